@@ -6,8 +6,13 @@ exact economy SVD (hand-written block Jacobi) -> rank-512 truncation / un-scale 
 Nothing is cached between steps.  N>1: one process per GPU (torchrun), each rank factorises its own batch — the path
 shards over independent matrices with no data-path collective (weak scaling); only barrier + max-reduce of the time.
 
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last timed step with --dump-outputs DIR, and prints
+the headline line.  --full adds everything else this file measures or checks: per-kernel profile and roofline, batch-1 latency,
+K9 reconstruction error, the CPU baseline and oracle parity, and the whole-model leg (`full_model` / `sharded_model`).
+
 Prints ONE JSON line on rank 0."""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -297,7 +302,7 @@ def dry_run(args, rank, world):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     sharded = None
-    if args.sharded_model != "none":
+    if args.full and args.sharded_model != "none":
         sharded = sharded_model_leg("tiny" if args.sharded_model == "auto" else args.sharded_model, rank, world, torch.device("cpu"), dry=True)
     if rank == 0:
         assert world == 1 or int(t[1].item()) == world - 1
@@ -307,6 +312,107 @@ def dry_run(args, rank, world):
                           "config": {"workload": "dry run: launch plumbing only", "batch_per_gpu": args.batch, "parallelism": f"independent matrices x{world}"}}))
     if world > 1:
         dist.destroy_process_group()
+
+
+def lib_sha256():
+    from asvd4llm_amd import _lib
+    return hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()
+
+
+def headline(args, world, dt, t0, step_marks, prewarm_steps, timed_infos):
+    """the part of the line every run prints (rank 0): the timed figure and what it was measured on"""
+    B, m, n, r = args.batch, args.m, args.n, args.rank
+    value = B * args.steps * world / dt
+    return {
+        "metric": "weight-matrix SVDs/sec (4096x4096 fp32)", "value": value, "unit": "SVD/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "prewarm_steps": prewarm_steps, "ms_per_step": 1e3 * dt / args.steps,
+        "step_wall_ms": [1e3 * (b - a) for a, b in zip([t0] + step_marks[:-1], step_marks)], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "arithmetic": "fp32 in, fp32 U / S / V out (the rank-r factors are emitted in fp16); inside: the Gram matrix of the Cholesky-QR EXACTLY from int8 digit products "
+                      "(24-bit fixed point per column, nine products, int32 accumulation, fp64 combine: csrc/gram_i8.h), the Cholesky factorisation in fp64 MFMA, fp32 VALU for the "
+                      "64x64 eigen-solves, the dense-sweep update + Gram as THREE fp16 MFMA products per fp32 product with power-of-two column scales (2^-22 relative per "
+                      "product), the coupling snapshot and the long-side GEMM as EIGHT int8 digit products with exact int32 accumulation (operands rounded to 2^-25 of "
+                      "their column / row maximum: csrc/snapshot_i8.h, csrc/nn_gemm_i8.h): fp32-equivalent by measurement, not by construction — per-column error against "
+                      "fp64 and int64 arithmetic in tests/test_gpu_twolevel.py / test_gpu_gram_i8.py, whole-SVD parity on flat AND graded / clustered inputs in "
+                      "tests/test_gpu_svd.py / test_gpu_families.py",
+        "config": {"workload": f"{B} synthetic {m}x{n} fp32 Linears per GPU per step, abs_mean scaling (alpha 0.5), full SVD + rank-{r} truncation, factors emitted in fp16 (SURVEY 8d; the reference would emit the Linear's own dtype, svd_linear.py:102 - the cast is <0.1% of a step)",
+                   "batch_per_gpu": B, "m": m, "n": n, "rank": r, "parallelism": f"independent matrices x{world}",
+                   "batch_split_over_chip_halves": bool(any(i.split for i in timed_infos)),
+                   "split_refused_device_shared_or_masked": bool(any(i.split_refused for i in timed_infos)),
+                   "split_note": "asvd_svd_batched runs a batch of >= 4 problems with >= 3072 columns as two halves on CU-masked streams (128 CUs each, one host "
+                                 "thread each; DESIGN.md 3.11) unless another process computes on the device: the flag above is what the TIMED steps did (path bits of the "
+                                 "library).  `roofline` (--full) = a profiled step that runs UNSPLIT, every kernel alone on the whole chip (what profiles/*kernel_stats* with "
+                                 "ASVD_SPLIT=0 shows); `roofline.split` = a profiled step in the timed configuration"},
+        "lib_sha256": lib_sha256(),
+        "lib_build": "prebuilt in-tree asvd4llm_amd/libasvd_hip.so loaded with ctypes; bench.py never compiles (__graft_entry__.build() compiles only when a source is newer than the .so)",
+    }
+
+
+def per_rank_rates(dt_local, batch, steps, world, comm_dev):
+    """N > 1: every rank's own SVDs/s over its own wall clock (host-side gather on the gloo group)"""
+    import torch
+    import torch.distributed as dist
+    mine = torch.tensor([batch * steps / dt_local], dtype=torch.float64, device=comm_dev)
+    allr = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(allr, mine)
+    return [float(t.item()) for t in allr]
+
+
+def device_inventory(dev, rank, local_rank, gpu_index, world):
+    """device inventory of the run (host-side gather on the gloo group): what a multi-GPU record must carry to be read later.  Every rank calls
+    it; rank 0 gets the record, the others None."""
+    import torch
+    import torch.distributed as dist
+    props = torch.cuda.get_device_properties(dev)
+    me = {"rank": rank, "local_rank": local_rank, "device_index": gpu_index, "name": props.name, "cus": props.multi_processor_count,
+          "pci_bus_id": "%04x:%02x:%02x" % (getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0), getattr(props, "pci_device_id", 0)),
+          "hostname_pid": f"{os.uname().nodename}:{os.getpid()}"}
+    everyone = [me]
+    if world > 1:
+        everyone = [None] * world
+        dist.all_gather_object(everyone, me)
+    if rank != 0:
+        return None
+    try:
+        rccl_v = ".".join(str(x) for x in torch.cuda.nccl.version())
+    except Exception:   # noqa: BLE001
+        rccl_v = None
+    return {"visible_device_count": torch.cuda.device_count(), "rccl_version": rccl_v, "per_rank": everyone,
+            "host_group_backend": "gloo" if world > 1 else "none (single process)"}
+
+
+DUMP_BUDGET = 64 << 20       # bytes of all files of --dump-outputs together
+DUMP_SAMPLE = 65536          # positions per problem of the sampled arrays (fewer when the batch would exceed the budget)
+DUMP_SEEDS = {"U": 11, "V": 12, "A": 13, "B": 14}
+
+
+def dump_outputs(path, U, S, V, scales, outs):
+    """--dump-outputs: what the last timed step handed to its caller, one float32 .npy per array, rows = the problems of the batch in order.
+    S.npy [B, k] and scales.npy [B, n] (the column scales the SVD ran on) whole, nan_flags.npy [B, 3] of the truncation; U / V (fp32 [m, k] /
+    [n, k]) and A / B (the emitted fp16 rank-r factors [m, r] / [r, n]) are too large whole (2 GB for U alone at the default size): each is
+    written as <name>_sample.npy [B, s], the same s positions of the row-major flattened array in every problem, drawn without replacement by
+    numpy's generator from a fixed seed per array and sorted — identical from run to run for the same --m / --n / --rank / --batch."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = len(S)
+    whole = {"S": torch.stack(S).float(), "scales": torch.stack(scales).float(), "nan_flags": torch.stack([o[2] for o in outs]).float()}
+    sampled = {"U": U, "V": V, "A": [o[0] for o in outs], "B": [o[1] for o in outs]}
+    left = DUMP_BUDGET - sum(4 * t.numel() for t in whole.values()) - 4096 * (len(whole) + len(sampled))   # .npy headers
+    per = max(1, min(DUMP_SAMPLE, left // (4 * B * len(sampled))))
+    arrays = {k: t.cpu().numpy() for k, t in whole.items()}
+    for name, mats in sampled.items():
+        numel = mats[0].numel()
+        idx = np.sort(np.random.default_rng(DUMP_SEEDS[name]).choice(numel, min(per, numel), replace=False))
+        idx_d = torch.from_numpy(idx).to(mats[0].device)
+        arrays[name + "_sample"] = torch.stack([x.reshape(-1).index_select(0, idx_d) for x in mats]).float().cpu().numpy()
+    total = 0
+    for name, a in arrays.items():
+        f = os.path.join(path, name + ".npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float32))
+        total += os.path.getsize(f)
+    assert total <= DUMP_BUDGET, total
+    return total
 
 
 def main():
@@ -319,6 +425,10 @@ def main():
     ap.add_argument("--n", type=int, default=4096)
     ap.add_argument("--rank", type=int, default=512)
     ap.add_argument("--prewarm_s", type=float, default=5.0, help="seconds of untimed identical work before the warm-up steps (0 disables)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as float32 DIR/<name>.npy (rank 0; at most 64 MB: see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: per-kernel profile and roofline, batch-1 latency, K9, CPU baseline "
+                    "and oracle parity, the whole-model leg (`full_model`; `sharded_model` at N > 1).  The options below apply to --full runs only")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_latency", action="store_true", help="skip the batch-1 latency leg (profiling runs: keeps per-kernel averages to the batch workload)")
     ap.add_argument("--cpu_reps", type=int, default=3, help="repetitions of the CPU oracle pipeline at the best thread count (>= 3; median reported)")
@@ -334,6 +444,8 @@ def main():
     ap.add_argument("--same_gpu", action="store_true", help="bind every rank to cuda:0 (with --dist_backend gloo)")
     ap.add_argument("--dry_run", action="store_true", help="launch plumbing only (CPU, gloo): spawn/bind ranks, barrier, max-reduce, JSON line; no kernels, value = null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` without a torchrun environment: launch the N ranks ourselves (one process per GPU, RCCL rendezvous on
     # 127.0.0.1) and let rank 0 of the children print the JSON line.  Under the driver's own `python -m torch.distributed.run ...`
@@ -426,6 +538,22 @@ def main():
     # the outputs every parity check below looks at are those of the LAST TIMED step (the split call when the batch qualifies), not of the profiled one
     U, S, V, scales, outs, timed_infos = res
     res = None
+    assert all(i.status == 0 for i in timed_infos), [i.status for i in timed_infos]  # every SVD of the timed batch converged
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, U, S, V, scales, outs)
+    if not args.full:
+        # a plain run ends here: the headline line, nothing measured besides the timed steps
+        per_rank = per_rank_rates(dt_local, B, args.steps, world, comm_dev) if world > 1 else None
+        out = headline(args, world, dt, t0, step_marks, prewarm_steps, timed_infos) if rank == 0 else None
+        devices = device_inventory(dev, rank, local_rank, gpu_index, world)
+        if rank == 0:
+            if per_rank is not None:
+                out["per_rank_svds_per_s"] = per_rank
+            out["devices"] = devices
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- per-kernel-class durations with HIP events on the launch stream (one extra, untimed, profiled step) ----
     ops.svd_profile(True)
     infos = step()[5]
@@ -450,18 +578,12 @@ def main():
             split_prof["pairs"] = split_tot["pairs"]
         del sp_res
 
-    # per-rank rates (N > 1): every rank's own SVDs/s over its own wall clock
-    per_rank = None
-    if world > 1:
-        mine = torch.tensor([B * args.steps / dt_local], dtype=torch.float64, device=comm_dev)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [float(t.item()) for t in allr]
+    per_rank = per_rank_rates(dt_local, B, args.steps, world, comm_dev) if world > 1 else None
 
     out = None
     if rank == 0:
-        total_svds = B * args.steps * world
-        value = total_svds / dt
+        out = headline(args, world, dt, t0, step_marks, prewarm_steps, timed_infos)
+        value = out["value"]
         f_svd = svd_flops(m, n)
         pairs_cnt = prof.pop("pairs")
         sweep_ms, sweep_rot = prof.pop("sweep_ms"), prof.pop("sweep_rotated")
@@ -493,8 +615,7 @@ def main():
         # on this workload — a kernel change since then prints null instead of a stale "measured" number
         traffic, traffic_src, mfma_busy, pmc_clock, pmc_per_svd, lib_sha = None, None, None, None, None, None
         try:
-            import hashlib
-            lib_sha = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()
+            lib_sha = out["lib_sha256"]
             pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
             if dom in pmc.get("kernels", {}) and (m, n, B) == (4096, 4096, pmc.get("batch")):
                 if pmc.get("lib_sha256") == lib_sha:
@@ -571,51 +692,15 @@ def main():
         roofline["sweep_rotated_pairs"] = sweep_rot
         roofline["classes"] = classes
         roofline["sweeps"] = [i.sweeps for i in infos]
-        out = {
-            "metric": "weight-matrix SVDs/sec (4096x4096 fp32)", "value": value, "unit": "SVD/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "prewarm_steps": prewarm_steps, "ms_per_step": 1e3 * dt / args.steps,
-            "step_wall_ms": [1e3 * (b - a) for a, b in zip([t0] + step_marks[:-1], step_marks)], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "arithmetic": "fp32 in, fp32 U / S / V out (the rank-r factors are emitted in fp16); inside: the Gram matrix of the Cholesky-QR EXACTLY from int8 digit products "
-                          "(24-bit fixed point per column, nine products, int32 accumulation, fp64 combine: csrc/gram_i8.h), the Cholesky factorisation in fp64 MFMA, fp32 VALU for the "
-                          "64x64 eigen-solves, the dense-sweep update + Gram as THREE fp16 MFMA products per fp32 product with power-of-two column scales (2^-22 relative per "
-                          "product), the coupling snapshot and the long-side GEMM as EIGHT int8 digit products with exact int32 accumulation (operands rounded to 2^-25 of "
-                          "their column / row maximum: csrc/snapshot_i8.h, csrc/nn_gemm_i8.h): fp32-equivalent by measurement, not by construction — per-column error against "
-                          "fp64 and int64 arithmetic in tests/test_gpu_twolevel.py / test_gpu_gram_i8.py, whole-SVD parity on flat AND graded / clustered inputs in "
-                          "tests/test_gpu_svd.py / test_gpu_families.py",
-            "config": {"workload": f"{B} synthetic {m}x{n} fp32 Linears per GPU per step, abs_mean scaling (alpha 0.5), full SVD + rank-{r} truncation, factors emitted in fp16 (SURVEY 8d; the reference would emit the Linear's own dtype, svd_linear.py:102 - the cast is <0.1% of a step)",
-                       "batch_per_gpu": B, "m": m, "n": n, "rank": r, "parallelism": f"independent matrices x{world}",
-                       "batch_split_over_chip_halves": bool(any(i.split for i in timed_infos)),
-                       "split_refused_device_shared_or_masked": bool(any(i.split_refused for i in timed_infos)),
-                       "split_note": "asvd_svd_batched runs a batch of >= 4 problems with >= 3072 columns as two halves on CU-masked streams (128 CUs each, one host "
-                                     "thread each; DESIGN.md 3.11) unless another process computes on the device: the flag above is what the TIMED steps did (path bits of the "
-                                     "library).  `roofline` = a profiled step that runs UNSPLIT, every kernel alone on the whole chip (what profiles/*kernel_stats* with "
-                                     "ASVD_SPLIT=0 shows); `roofline.split` = a profiled step in the timed configuration"},
-            "roofline": roofline,
-            "lib_sha256": lib_sha,
-            "lib_build": "prebuilt in-tree asvd4llm_amd/libasvd_hip.so loaded with ctypes; bench.py never compiles (__graft_entry__.build() compiles only when a source is newer than the .so)",
-        }
+        out["roofline"] = roofline
         if per_rank is not None:
             out["per_rank_svds_per_s"] = per_rank
 
-    # ---- device inventory of the run (host-side gather on the gloo group): what the first multi-GPU record must carry to be read later ----
-    props = torch.cuda.get_device_properties(dev)
-    me = {"rank": rank, "local_rank": local_rank, "device_index": gpu_index, "name": props.name, "cus": props.multi_processor_count,
-          "pci_bus_id": "%04x:%02x:%02x" % (getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0), getattr(props, "pci_device_id", 0)),
-          "hostname_pid": f"{os.uname().nodename}:{os.getpid()}"}
-    everyone = [me]
-    if world > 1:
-        everyone = [None] * world
-        dist.all_gather_object(everyone, me)
+    devices = device_inventory(dev, rank, local_rank, gpu_index, world)
     if rank == 0:
-        try:
-            rccl_v = ".".join(str(x) for x in torch.cuda.nccl.version())
-        except Exception:   # noqa: BLE001
-            rccl_v = None
-        out["devices"] = {"visible_device_count": torch.cuda.device_count(), "rccl_version": rccl_v, "per_rank": everyone,
-                          "host_group_backend": "gloo" if world > 1 else "none (single process)"}
+        out["devices"] = devices
         for h in out["roofline"].get("split", {}).get("halves", []):
-            h["cus"] = props.multi_processor_count // 2
+            h["cus"] = devices["per_rank"][0]["cus"] // 2
 
     # The line is complete from here on.  Everything below is an untimed extra; a watchdog prints the line and ends the process if an extra does not
     # come back (a collective that has never run on this node must not cost the weak-scaling number).  ONE printer: whoever takes the lock first.

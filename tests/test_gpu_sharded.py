@@ -157,7 +157,7 @@ def test_bench_two_ranks_on_one_gpu_run_the_whole_multi_gpu_leg(tmp_path):
     from tests.conftest import ROOT
     import os
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist_backend", "gloo", "--same_gpu", "--batch", "4", "--steps", "1", "--warmup", "1",
-           "--prewarm_s", "0", "--sharded_model", "llama-7b-2layers"]
+           "--prewarm_s", "0", "--full", "--sharded_model", "llama-7b-2layers"]
     env = dict(os.environ, ASVD_STRICT="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1100, env=env, cwd=str(tmp_path))
@@ -191,7 +191,7 @@ def test_bench_keeps_the_line_when_the_rccl_group_cannot_be_created(tmp_path):
     from tests.conftest import ROOT
     import os
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist_backend", "nccl", "--same_gpu", "--batch", "4", "--steps", "1", "--warmup", "1",
-           "--prewarm_s", "0", "--sharded_model", "llama-7b-2layers"]
+           "--prewarm_s", "0", "--full", "--sharded_model", "llama-7b-2layers"]
     env = dict(os.environ, ASVD_STRICT="1", ASVD_BENCH_FAIL_NCCL="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1100, env=env, cwd=str(tmp_path))
@@ -217,7 +217,7 @@ def test_bench_watchdog_keeps_the_line_when_the_sharded_leg_does_not_come_back(t
     import sys
     from tests.conftest import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist_backend", "gloo", "--same_gpu", "--batch", "4", "--steps", "1", "--warmup", "0",
-           "--prewarm_s", "0", "--sharded_model", "llama-7b-2layers", "--sharded_timeout_s", "0.05"]
+           "--prewarm_s", "0", "--full", "--sharded_model", "llama-7b-2layers", "--sharded_timeout_s", "0.05"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=800, env=env, cwd=str(tmp_path))
