@@ -23,14 +23,13 @@
 //                           four independent pairs per workgroup;
 //           evdw12_kernel — BOTH inner steps of a super-pair in one launch (two waves: sub-pairs (0,2) (1,3), then (0,3) (1,2)); the
 //                           step-0 eigenvectors and diagonal blocks stay in LDS, the epilogue emits Qfin and the carried blocks.
-//                           Template RINGM: which inner steps visit only the 1024 CROSS pairs of their two panels, on a ring of interleaved
-//                           positions in 32 phases instead of 64 (evdw_sweep_ring; round 5).  Default from 2048 columns on: step 1 (its panels
-//                           arrive with exactly diagonal Gram blocks — step 0 has just diagonalised them — so the visit gives up nothing).
+//                           Template RING1: inner step 1 visits only the 1024 CROSS pairs of its two panels, on a ring of interleaved
+//                           positions in 32 phases instead of 64 (evdw_sweep_ring; round 5).  Default from 2048 columns on (its panels arrive
+//                           with exactly diagonal Gram blocks — step 0 has just diagonalised them — so the visit gives up nothing).
 
 #include "common.h"
 #include "jacobi_shared.h"
 #include <cstdlib>
-#include <cstdio>
 
 namespace {
 using namespace asvdk;
@@ -627,7 +626,7 @@ __global__ __launch_bounds__(256, 2) void evdw0_kernel(Sched sc, const float* __
     const int64_t slot = (int64_t)b * npairs + pair;
     int* act_flag = active + slot;
     int I, J;
-    if (!get_pair(sc, plist, list_stride, b, nb, step, pair, I, J)) {  // padding pair / empty slot: nothing to rotate
+    if (!get_pair(plist, list_stride, b, nb, step, pair, I, J)) {  // padding pair / empty slot: nothing to rotate
         if (lane == 0 && hw == 0) *act_flag = 0;
         return;
     }
@@ -675,10 +674,6 @@ __global__ __launch_bounds__(256, 2) void evdw0_kernel(Sched sc, const float* __
         atomicMax(&maxoff_bits[b], is_nan ? 0x7fc00000u : __float_as_uint(offt));
         *act_flag = rotate ? 1 : 0;
         if (rotate && offt >= tol) atomicAdd(&nrot[b], 1);
-        if (v3.hist && !is_nan) {  // debug: decade histogram of the pair measure (ASVD_DEBUG_HIST)
-            const int bk = (int)floorf(-log10f(fmaxf(off0, 1e-30f)));
-            atomicAdd(&v3.hist[bk < 0 ? 0 : (bk > 9 ? 9 : bk)], 1);
-        }
     }
     float* d0 = KEEPG ? v3.Gd32 + ((int64_t)b * v3.nbpan + I) * 1024 : nullptr;
     float* d1 = KEEPG ? v3.Gd32 + ((int64_t)b * v3.nbpan + J) * 1024 : nullptr;
@@ -739,20 +734,13 @@ __device__ __forceinline__ int mfma_row(int reg, int h) { return (reg & 3) + 8 *
 // NW = 1: two waves per super-pair, each solve wave-local (throughput form).  NW = 4: eight waves, waves 0 / 1 are the MAIN waves of the two
 // solves and run exactly the code of the NW = 1 form except that their sweeps are cooperative (coop_sweep) with the helper waves
 // 2 h + sp, h = 1..3, which only take part in the sweeps and the workgroup barriers (latency form: one workgroup per CU).
-// RING: both inner steps are cross-only visits on the ring (evdw_sweep_ring / coop_sweep<NW, true>): half the phases per solve.
-template <int NW, int RINGM>   // RINGM: 0 full visits, 1 cross-only ring visits in both inner steps, 2 in step 1 only
+// RING1: inner step 1 is a cross-only visit on the ring (evdw_sweep_ring / coop_sweep<NW, true>): half the phases of its solve.  (Cross-only
+// in BOTH inner steps did not converge in reasonable time: 10-11 sweeps, profiles/r5_ring.txt; removed.)
+template <int NW, bool RING1>
 __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched sc, unsigned* __restrict__ maxoff_bits, int* __restrict__ nrot,
                                                         const int* __restrict__ done, float tol, int inner_sweeps, int nb, int step, int kb,
-                                                        EvdV3 v3, long long* __restrict__ trace) {
+                                                        EvdV3 v3) {
     extern __shared__ __attribute__((aligned(16))) float e12_smem[];
-    constexpr bool RING0 = RINGM == 1, RING1 = RINGM >= 1;
-    // stage trace (ASVD_EVDW_TRACE=1): shader-clock stamps of workgroup (0, 0), one row of 16 per wave
-    int tstage = 0;
-    auto stamp = [&]() {
-        if (trace && blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x & 63) == 0) trace[(threadIdx.x >> 6) * 16 + tstage] = (long long)__builtin_amdgcn_s_memtime();
-        ++tstage;
-    };
-    stamp();
     float* const R16 = e12_smem;                // multi-purpose region (see above)
     const int tid = threadIdx.x, lane = tid & 63, wv_ = __builtin_amdgcn_readfirstlane(tid >> 6), sp = wv_ & 1, hw = wv_ >> 1;
     const int hi = lane >> 5, cc = lane & 31;
@@ -781,7 +769,7 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
     if constexpr (NW > 1) {
         if (hw > 0) {   // helper wave: the two cooperative sweeps and the barriers of the main waves in between, nothing else
             float dd = 0.0f;
-            coop_sweep<NW, RING0>(g, q, dd, 0.0f, false, lane, hw, LC);
+            coop_sweep<NW>(g, q, dd, 0.0f, false, lane, hw, LC);
             __syncthreads(); __syncthreads();                       // end of step 0
             __syncthreads(); __syncthreads(); __syncthreads();      // step-1 image assembly
             coop_sweep<NW, RING1>(g, q, dd, 0.0f, false, lane, hw, LC);
@@ -822,7 +810,6 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
 #pragma unroll
             for (int r = 0; r < 32; ++r) g[32 + r] = tr[r * 33 + cc];  // G[32 + r][cc] = C[cc][r]
         }
-        stamp();  // 1: image loaded
         evdw_init_state(g, lane, diag, bpiv);
         if (v3.Din) v3.Din[slot * 128 + (lane < 32 ? 32 * sp + lane : 64 + 32 * sp + (lane - 32))] = diag;   // pre-rotation squared column norms, Q order
         evdw_measure(g, diag, lane, I < kb, J < kb, off0, offt);
@@ -832,24 +819,16 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
             atomicMax(&maxoff_bits[b], is_nan ? 0x7fc00000u : __float_as_uint(offt));
             sub[sp] = rotate ? 1 : 0;
             if (rotate && offt >= tol) atomicAdd(&nrot[b], 1);
-            if (v3.hist && !is_nan) {  // debug: decade histogram of the pair measure (ASVD_DEBUG_HIST)
-                const int bk = (int)floorf(-log10f(fmaxf(off0, 1e-30f)));
-                atomicAdd(&v3.hist[bk < 0 ? 0 : (bk > 9 ? 9 : bk)], 1);
-            }
         }
         evdw_identity(q, lane);
-        stamp();  // 2: measured
         asm volatile("" ::: "memory");
-        if constexpr (NW > 1) coop_sweep<NW, RING0>(g, q, diag, bpiv, rotate, lane, 0, LC);
+        if constexpr (NW > 1) coop_sweep<NW>(g, q, diag, bpiv, rotate, lane, 0, LC);
         else if (rotate) {
             const int nsw = (off0 > 0.05f) ? inner_sweeps : min(1, inner_sweeps);
-            if constexpr (RING0) evdw_sweep_ring(g, q, diag, bpiv, lane, nsw, e12_smem + E12_CS + sp * 128);
-            else evdw_sweep(g, q, diag, bpiv, lane, nsw * EVD_PHASE_PAIRS, e12_smem + E12_CS + sp * 128);
+            evdw_sweep(g, q, diag, bpiv, lane, nsw * EVD_PHASE_PAIRS, e12_smem + E12_CS + sp * 128);
         }
         asm volatile("" ::: "memory");   // no load of a later stage is hoisted above the sweep (its registers would be spilled across it)
-        stamp();  // 3: swept
         evdw_finish(q, diag, lane, rotate, cs, rnk);
-        stamp();  // 4: norms + ranks
         // sorted, rescaled eigenvectors, row-major 64 x 64 in global memory: column `lane` goes to column rnk (a permutation inside a 256-byte row)
         float* __restrict__ qdst = v3.Q0 + (slot * 2 + sp) * (PW * PW) + rnk;
 #pragma unroll
@@ -858,9 +837,7 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
         // transformed diagonal blocks: sorted positions 0..31 -> block sp, 32..63 -> block 2 + sp
         evdw_store_diag_blocks(g, diag, cs, rnk, lane, R16 + sp * 1024, R16 + (2 + sp) * 1024);
     }
-    stamp();  // 5: Q0 + diagonal blocks stored
     __syncthreads();   // diagonal blocks of both solves are in LDS, both Q0 in global memory (stores acknowledged: workgroup-scope release)
-    stamp();  // 6
 
     // ================================ step 1: sub-pair (sp, 3 - sp) ================================
     const int I1 = 2 * S + sp, J1 = 2 * T + (1 - sp);
@@ -907,7 +884,6 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
         }
     }
     __syncthreads();
-    stamp();  // 7: M assembled
     f32x16 cacc = {0};
     {
         // T = MM QBh (64 x 32, K = 64):  MM = M (sp 0) or M^T (sp 1);  QBh = second half of the OTHER solve's Q0
@@ -953,10 +929,8 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
             for (int r = 0; r < 32; ++r) g[32 + r] = Cs[cc1 * 33 + r];     // G[32 + r][cc1] = C'[cc1][r]
         }
     }
-    stamp();  // 8: cross block computed, image complete
     evdw_init_state(g, lane1, diag, bpiv);
     evdw_measure(g, diag, lane1, I1 < kb, J1 < kb, off0, offt);
-    stamp();  // 9: measured
     asm volatile("" ::: "memory");
     {
         const bool is_nan = off0 != off0;
@@ -965,10 +939,6 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
             atomicMax(&maxoff_bits[b], is_nan ? 0x7fc00000u : __float_as_uint(offt));
             sub[2 + sp] = rotate ? 1 : 0;
             if (rotate && offt >= tol) atomicAdd(&nrot[b], 1);
-            if (v3.hist && !is_nan) {  // debug: decade histogram of the pair measure (ASVD_DEBUG_HIST)
-                const int bk = (int)floorf(-log10f(fmaxf(off0, 1e-30f)));
-                atomicAdd(&v3.hist[bk < 0 ? 0 : (bk > 9 ? 9 : bk)], 1);
-            }
         }
         evdw_identity(q, lane1);
         if constexpr (NW > 1) coop_sweep<NW, RING1>(g, q, diag, bpiv, rotate, lane1, 0, LC);
@@ -978,10 +948,8 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
             else evdw_sweep(g, q, diag, bpiv, lane1, nsw * EVD_PHASE_PAIRS, e12_smem + E12_CS + sp * 128);
         }
         asm volatile("" ::: "memory");
-        stamp();  // 10: swept
         evdw_finish(q, diag, lane1, rotate, cs, rnk);
     }
-    stamp();  // 11
     // thread index opaque once more: the per-lane addresses of the epilogue are not computed (and kept live) before the step-1 sweep
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));
@@ -989,7 +957,6 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
     // new carried diagonal blocks of the two panels
     evdw_store_diag_blocks(g, diag, cs, rnk, lane2, v3.Gd32 + ((int64_t)b * v3.nbpan + I1) * 1024, v3.Gd32 + ((int64_t)b * v3.nbpan + J1) * 1024);
 
-    stamp();  // (between 11 and 12): diagonal blocks stored
     // Qfin[:, columns of blocks (ba, bb)] = Q^(0)[:, {ba, bb}] Q1,  ba = sp, bb = 3 - sp:
     //   rows of blocks {ba, ba + 2}  <-  Q0_ba[:, :32]       Q1[:32, :]        (product 0)
     //   rows of blocks {bb - 2, bb}  <-  Q0_(bb-2)[:, 32:]   Q1[32:, :]        (product 1)
@@ -1041,7 +1008,6 @@ __global__ __launch_bounds__(128 * NW, NW == 1 ? 2 : 1) void evdw12_kernel(Sched
             }
         }
     }
-    stamp();  // 12: Qfin written
 }
 
 // Test hook kernel: one wave per 64x64 symmetric matrix (row-major), `sweeps` full inner sweeps, outputs the UNSORTED eigenvector
@@ -1114,60 +1080,39 @@ constexpr int EVDQ_NW = 4;
 static int evdq12_lds_bytes() { return (int)((E12_SMEM_FLOATS + 2 * Coop<EVDQ_NW>::FLOATS) * sizeof(float)); }
 
 void launch_evdw12(int npairs_s, int batch, hipStream_t st, const Sched& sc, unsigned* maxoff_bits, int* nrot, const int* done, float tol,
-                   int inner_sweeps, int nb, int step, int kb, const EvdV3& v3, int sweep, int ring_default) {
+                   int inner_sweeps, int nb, int step, int kb, const EvdV3& v3, bool ring_default) {
     // the > 64 KB dynamic-LDS opt-in is per device: one flag per device the process drives (idempotent; a race only repeats the calls)
     static bool attr_done[64] = {};
     int devid = 0;
     (void)hipGetDevice(&devid);
     if (devid < 0 || devid >= 64 || !attr_done[devid]) {
         bool ok = true;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, evdw12_lds_bytes()) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, evdw12_lds_bytes()) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, evdw12_lds_bytes()) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<EVDQ_NW, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, evdq12_lds_bytes()) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<EVDQ_NW, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, evdq12_lds_bytes()) == hipSuccess;
-        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<EVDQ_NW, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, evdq12_lds_bytes()) == hipSuccess;
+        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, evdw12_lds_bytes()) == hipSuccess;
+        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, evdw12_lds_bytes()) == hipSuccess;
+        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<EVDQ_NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, evdq12_lds_bytes()) == hipSuccess;
+        ok = ok && hipFuncSetAttribute((const void*)evdw12_kernel<EVDQ_NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, evdq12_lds_bytes()) == hipSuccess;
         if (ok && devid >= 0 && devid < 64) attr_done[devid] = true;
     }
     // latency form when the launch cannot even give every CU one workgroup: four waves per solve (bit-identical results).  It needs one
     // full inner sweep per visit (the default) and the standard 32 phase pairs.  ASVD_EVDQ=0 / 1 forces the choice.
     const bool coop = inner_sweeps == 1 && (evdq_env() == 1 || (evdq_env() != 0 && (long long)npairs_s * batch <= call_cus_now()));
-    static long long* trace = nullptr;
-    static int traced = 0;
-    if (getenv("ASVD_EVDW_TRACE") && !trace) (void)hipMalloc(&trace, 16 * 16 * sizeof(long long));
-    long long* tr = traced < 3 ? trace : nullptr;
-    // cross-only visits on the ring (evdw_sweep_ring).  ring_default (the driver's choice): 2 = inner step 1 cross-only — its two panels arrive with
-    // exactly diagonal Gram blocks, step 0 has just diagonalised them, so the visit loses nothing at its start — for problems of >= 2048 columns:
+    // cross-only visit of inner step 1 on the ring (evdw_sweep_ring).  ring_default (the driver's choice): its two panels arrive with exactly
+    // diagonal Gram blocks, step 0 has just diagonalised them, so the visit loses nothing at its start — for problems of >= 2048 columns:
     // measured +2 % at 32 x 4096^2 (eigen-solves 108 -> 91.5 ms per step, a tiny ninth sweep for some problems), +5 % at 32 x 2048^2, -10 % on the
-    // latency of a lone 4096^2 (95.5 -> 86.3 ms); 768-column problems lose 7 % (one more sweep of 12 super-panels) and keep full visits.  Cross-only
-    // in BOTH steps (mode 1) does not converge in reasonable time: 10-11 sweeps, 8 of them dense (profiles/r5_ring.txt).
-    // Measurement knobs: ASVD_RING=0 / 1 / 2 forces the mode, ASVD_RING_FROM=k applies it from dense sweep k on.
+    // latency of a lone 4096^2 (95.5 -> 86.3 ms); 768-column problems lose 7 % (one more sweep of 12 super-panels) and keep full visits.
+    // ASVD_RING=2 forces the ring visit (tests reach it below 2048 columns); unset or any other value keeps the driver's choice.
     const char* er = getenv("ASVD_RING");
-    const char* ef = getenv("ASVD_RING_FROM");
-    const int ring = er ? ((sweep >= (ef ? atoi(ef) : 0)) ? atoi(er) : 0) : ring_default;
+    const bool ring = (er && atoi(er) == 2) || ring_default;
     const dim3 grid((unsigned)npairs_s, (unsigned)batch);
-#define ASVD_E12(NWV, RM, THREADS, LDS) evdw12_kernel<NWV, RM><<<grid, THREADS, LDS, st>>>(sc, maxoff_bits, nrot, done, tol, inner_sweeps, nb, step, kb, v3, tr)
+#define ASVD_E12(NWV, RING, THREADS, LDS) evdw12_kernel<NWV, RING><<<grid, THREADS, LDS, st>>>(sc, maxoff_bits, nrot, done, tol, inner_sweeps, nb, step, kb, v3)
     if (coop) {
-        if (ring == 1) ASVD_E12(EVDQ_NW, 1, 128 * EVDQ_NW, evdq12_lds_bytes());
-        else if (ring == 2) ASVD_E12(EVDQ_NW, 2, 128 * EVDQ_NW, evdq12_lds_bytes());
-        else ASVD_E12(EVDQ_NW, 0, 128 * EVDQ_NW, evdq12_lds_bytes());
+        if (ring) ASVD_E12(EVDQ_NW, true, 128 * EVDQ_NW, evdq12_lds_bytes());
+        else ASVD_E12(EVDQ_NW, false, 128 * EVDQ_NW, evdq12_lds_bytes());
     } else {
-        if (ring == 1) ASVD_E12(1, 1, 128, evdw12_lds_bytes());
-        else if (ring == 2) ASVD_E12(1, 2, 128, evdw12_lds_bytes());
-        else ASVD_E12(1, 0, 128, evdw12_lds_bytes());
+        if (ring) ASVD_E12(1, true, 128, evdw12_lds_bytes());
+        else ASVD_E12(1, false, 128, evdw12_lds_bytes());
     }
 #undef ASVD_E12
-    if (tr) {
-        long long h[32];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, trace, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 2; ++w) {   // the two main waves
-            fprintf(stderr, "[evdw12 trace] launch %d (%s) wave %d stage deltas (clocks):", traced, coop ? "four waves per solve" : "wave-local", w);
-            for (int i = 1; i < 14; ++i) fprintf(stderr, " %lld", h[w * 16 + i] - h[w * 16 + i - 1]);
-            fprintf(stderr, "\n");
-        }
-        ++traced;
-    }
 }
 
 void launch_evdw_test(int batch, hipStream_t st, const float* G, int sweeps, float* Q, float* diag, int* rnk, float* cs, float* Gout, float* meas) {

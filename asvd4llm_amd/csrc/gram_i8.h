@@ -124,35 +124,15 @@ constexpr int GI_STAGE_BYTES = 2 * 3 * 4 * 4 * 512;  // side, digit, panel, row 
 __global__ __launch_bounds__(512) void gram_i8_kernel(const signed char* __restrict__ planes, int64_t plane_stride, int nb, int kgs, int n_pad,
                                                       const int* __restrict__ ex, double* __restrict__ G, int64_t ldg, int64_t g_batch_stride,
                                                       int accumulate, int nt, const double* __restrict__ dp /* nullable: G_ij / (dp_i dp_j) is stored;
-                                                      a column with dp = 0 gets a unit diagonal and zeros */, int order /* block order: 0 row runs per XCD, 1 4 x 8 groups per XCD, 2 plain */) {
+                                                      a column with dp = 0 gets a unit diagonal and zeros */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // 2 x GI_STAGE_BYTES
     // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs; give every XCD a contiguous run of blocks (they share I panels in its L2)
-    // (a block count that is not a multiple of 8 keeps the plain order: correct, merely less local)
+    // (a block count that is not a multiple of 8 keeps the plain order: correct, merely less local).  Row runs per XCD; 4 x 8 groups of blocks per
+    // XCD and the plain order were measured against it (tools/bench_i8_gemm.py, round 6) and removed.
     const int total = gridDim.x;
-    const int lid = ((total & 7) || order == 2) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3));
+    const int lid = (total & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3));
     int Ib = 0, Jb = 0;
-    if (order == 1) {
-        // 4 x 8 groups of blocks (the 32 workgroups an XCD runs at a time share 4 I-side and 8 J-side column blocks in its L2), groups row by row
-        int rem = lid;
-        bool found = false;
-        for (int SI = 0; SI * 4 < nt && !found; ++SI)
-            for (int SJ = (SI * 4) >> 3; SJ * 8 < nt && !found; ++SJ) {
-                int cnt = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int ib = SI * 4 + i, lo = max(SJ * 8, ib), hi = min(SJ * 8 + 8, nt);
-                    if (ib < nt && hi > lo) cnt += hi - lo;
-                }
-                if (rem >= cnt) { rem -= cnt; continue; }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int ib = SI * 4 + i, lo = max(SJ * 8, ib), hi = min(SJ * 8 + 8, nt);
-                    const int wdt = (ib < nt && hi > lo) ? hi - lo : 0;
-                    if (!found && rem < wdt) { Ib = ib; Jb = lo + rem; found = true; }
-                    if (!found) rem -= wdt;
-                }
-            }
-    } else {
+    {
         int rem = lid;
         while (rem >= nt - Ib) { rem -= nt - Ib; ++Ib; }
         Jb = Ib + rem;

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void gram_kernel(Sched sc, const float* __rest
     const int nsplit = gridDim.x, npairs = gridDim.y;
     if (ld_flag(done + b)) return;
     int I, J;
-    if (!get_pair(sc, plist, list_stride, b, nb, step, pair, I, J)) return;
+    if (!get_pair(plist, list_stride, b, nb, step, pair, I, J)) return;
     const float* __restrict__ XI = X + (int64_t)b * batch_stride + (int64_t)I * panel_stride;
     const float* __restrict__ XJ = X + (int64_t)b * batch_stride + (int64_t)J * panel_stride;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void update_kernel(Sched sc, float* __restrict
     const int chunk = blockIdx.x, pair = blockIdx.y, b = blockIdx.z, npairs = gridDim.y;
     if (ld_flag(done + b) || !ld_flag(active + b * npairs + pair)) return;
     int I, J;
-    if (!get_pair(sc, plist, list_stride, b, nb, step, pair, I, J)) return;
+    if (!get_pair(plist, list_stride, b, nb, step, pair, I, J)) return;
     float* __restrict__ XI = X + (int64_t)b * batch_stride + (int64_t)I * panel_stride;
     float* __restrict__ XJ = X + (int64_t)b * batch_stride + (int64_t)J * panel_stride;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -465,9 +465,9 @@ __global__ __launch_bounds__(256) void backsolve_kernel(const float* __restrict_
 }
 
 // --------------------------------------------------------------------------------------------------
-// finalize 1: column norms (double accumulation), sigma_j = |a_j| / |v_j| (drift-corrected) or |a_j|
+// finalize 1: column norms (double accumulation), sigma_j = |a_j|
 __global__ __launch_bounds__(256) void colnorm_kernel(const float* __restrict__ X, int64_t panel_stride, int64_t batch_stride,
-                                                      int m_pad, int R, int n_pad, int sig_ratio, float* __restrict__ sig,
+                                                      int m_pad, int R, int n_pad, float* __restrict__ sig,
                                                       float* __restrict__ inv_na, float* __restrict__ inv_nv) {
     const int blk = blockIdx.x, b = blockIdx.y;
     const float* P = X + (int64_t)b * batch_stride + (int64_t)blk * panel_stride;
@@ -489,9 +489,7 @@ __global__ __launch_bounds__(256) void colnorm_kernel(const float* __restrict__ 
         for (int i = 1; i < 8; ++i) { sa += ra[i][c]; sv += rv[i][c]; }
         const double na = sqrt(sa), nv = sqrt(sv);
         const int j = blk * PB + c;
-        double s = na;
-        if (sig_ratio) s = (nv > 0.0) ? na / nv : 0.0;  // accumulated V: drift-corrected sigma = |a_j| / |v_j|
-        sig[(int64_t)b * n_pad + j] = (float)s;
+        sig[(int64_t)b * n_pad + j] = (float)na;
         inv_na[(int64_t)b * n_pad + j] = (na > 0.0) ? (float)(1.0 / na) : 0.0f;
         inv_nv[(int64_t)b * n_pad + j] = (nv > 0.0) ? (float)(1.0 / nv) : 0.0f;
     }

@@ -11,19 +11,16 @@ constexpr int PB = 32;       // panel width
 constexpr int PW = 2 * PB;   // pair width
 constexpr int EVD_PHASE_PAIRS = PW / 2;   // (A, B) phase pairs of one inner sweep of the 64x64 eigen-solve: one full odd-even cycle, every column pair meets once
 
-// Pair ordering of one Jacobi sweep: nb (even) panels, nb-1 steps, pair k in [0, nb/2) of step `step`.
-//  * default: XOR ordering over the panel count padded to a power of two P — step d = step+1 (d = 1..P-1) pairs every panel i
-//    with i^d; pairs that touch a padding panel (J >= nb) are skipped.  Steps 1, 2, 3, ... meet the nearest neighbours first,
-//    which on the norm-sorted, Cholesky-preconditioned matrices is where the coupling is: measured 10 -> 8 sweeps at 4096^2
-//    and 14 -> 9 on the row-scaled wide layers against the round-robin tournament (CPU prototype at n = 1024: 8 -> 6).
-//  * c_pair_order = 0 (ASVD_ORDER=rr, for A/B measurements): round-robin tournament (circle method), nb-1 steps of nb/2 pairs.
+// Pair ordering of one Jacobi sweep: XOR ordering over the panel count padded to a power of two P — step d = step+1 (d = 1..P-1) pairs
+// every panel i with i^d; pairs that touch a padding panel (J >= nb) are skipped.  Steps 1, 2, 3, ... meet the nearest neighbours first,
+// which on the norm-sorted, Cholesky-preconditioned matrices is where the coupling is: measured 10 -> 8 sweeps at 4096^2 and 14 -> 9 on the
+// row-scaled wide layers against the round-robin tournament (CPU prototype at n = 1024: 8 -> 6; the tournament was removed with its switch).
 // Everything a kernel needs to know about the call's pair schedules travels BY VALUE in its argument list (under 300 bytes of kernarg): round 2
 // kept these in __constant__ symbols rewritten by every call, so two concurrent calls with different shapes (a grouped 13B schedule next
 // to an XOR one) overwrote each other's tables mid-flight.
-//   pair_order  1 XOR (default), 0 round-robin (ASVD_ORDER=rr)
 //   super_order 1 XOR, 2 grouped (below);  gm / gpair: group pairs per round / {gA, gB} of the grouped schedule
 struct Sched {
-    int pair_order, super_order, gm;
+    int super_order, gm;
     int gb;         // grouped schedule: log2 of the group size G (1..4)
     int meas;       // measurement builds only (-DASVD_SG_TIMING, tools/bench_supgram.py): timing-only ablation bits of the fused kernel; 0 in the product
     signed char gpair[16][8][2];
@@ -31,24 +28,16 @@ struct Sched {
 static Sched default_sched() {
     Sched sc;
     std::memset(&sc, 0, sizeof(sc));
-    sc.pair_order = 1;
     sc.super_order = 1;
     return sc;
 }
 
-static __device__ __forceinline__ void rr_pair(const Sched& sc, int nb, int step, int k, int& I, int& J) {
-    if (sc.pair_order) {  // pair space padded to the next power of two: callers skip pairs with J >= nb
-        const int d = step + 1;
-        const int h = 31 - __clz(d);  // highest set bit of d: i < i^d  <=>  bit h of i is clear
-        I = ((k >> h) << (h + 1)) | (k & ((1 << h) - 1));
-        J = I ^ d;
-        return;
-    }
-    const int a = (k == 0) ? 0 : 1 + (k - 1 + step) % (nb - 1);
-    const int pb = nb - 1 - k;
-    const int b = 1 + (pb - 1 + step) % (nb - 1);
-    I = a < b ? a : b;
-    J = a < b ? b : a;
+// pair space padded to the next power of two: callers skip pairs with J >= nb
+static __device__ __forceinline__ void xor_pair(int step, int k, int& I, int& J) {
+    const int d = step + 1;
+    const int h = 31 - __clz(d);  // highest set bit of d: i < i^d  <=>  bit h of i is clear
+    I = ((k >> h) << (h + 1)) | (k & ((1 << h) - 1));
+    J = I ^ d;
 }
 
 // Pair ordering at the SUPER-PANEL level of the two-level sweeps (twolevel.h).  `step` counts from 0; pairs with T >= ns (padding) are skipped
@@ -90,7 +79,7 @@ static __device__ __forceinline__ void super_pair(const Sched& sc, int ns, int s
 
 // Pair handled by a workgroup: from the schedule (plist == nullptr) or, in sparse sweeps, from an explicit per-problem list of
 // marked pairs (code = I << 16 | J, -1 = empty slot).  Returns false when there is nothing to do for this slot.
-static __device__ __forceinline__ bool get_pair(const Sched& sc, const int* __restrict__ plist, int list_stride, int b, int nb, int step, int pair, int& I, int& J) {
+static __device__ __forceinline__ bool get_pair(const int* __restrict__ plist, int list_stride, int b, int nb, int step, int pair, int& I, int& J) {
     if (plist) {
         const int code = ld_flag(plist + b * list_stride + pair);
         if (code < 0) return false;
@@ -98,7 +87,7 @@ static __device__ __forceinline__ bool get_pair(const Sched& sc, const int* __re
         J = code & 0xffff;
         return true;
     }
-    rr_pair(sc, nb, step, pair, I, J);
+    xor_pair(step, pair, I, J);
     return J < nb;  // padding pair of the XOR ordering
 }
 
@@ -134,7 +123,6 @@ struct EvdV3 {
     float* D0;            // [slot][4][32*32]
     float* Qfin;          // [slot][128*128]
     int* subact;          // [slot][4]: step 0 sub-pairs 0,1; step 1 sub-pairs 0,1
-    int* hist;            // debug (ASVD_DEBUG_HIST): 10 counters, decade histogram of the pair measures of a sweep; nullptr otherwise
     float* Din;           // [slot][128]: squared column norms of the super-pair BEFORE its rotation (carried diagonal), in Q order (blocks S0 S1 T0 T1):
                           //              the power-of-two column scales of the split-fp16 update (twolevel.h, supgram_kernel) come from these
 };
@@ -152,7 +140,7 @@ void launch_evdw0(bool keepg, int npairs, int batch, hipStream_t st, const Sched
                   int list_stride, const EvdV3& v3);
 // both inner steps of every super-pair of super-step `step` (the work of evd_kernel<1,1> + evd_kernel<2,1>), two waves per super-pair
 void launch_evdw12(int npairs_s, int batch, hipStream_t st, const Sched& sc, unsigned* maxoff_bits, int* nrot, const int* done, float tol,
-                   int inner_sweeps, int nb, int step, int kb, const EvdV3& v3, int sweep = 0, int ring_default = 0);
+                   int inner_sweeps, int nb, int step, int kb, const EvdV3& v3, bool ring_default);
 int evdw12_lds_bytes();
 // test hook
 void launch_evdw_test(int batch, hipStream_t st, const float* G, int sweeps, float* Q, float* diag, int* rnk, float* cs, float* Gout, float* meas);

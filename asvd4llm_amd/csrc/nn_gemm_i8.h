@@ -158,14 +158,14 @@ __global__ __launch_bounds__(256) void split_v_i8_kernel(TallBatch tb, int cols,
 
 // out[z][r0 + ..][..] = Y.  Workgroup = 512 threads = one 128 (rows) x 128 (columns) block on the tiling of gram_i8_kernel: wave w owns row panels
 // 4 Ib + 2 (w >> 2) + {0, 1} against column panel 4 Jb + (w & 3) — 2 tiles x 4 weights x 16 = 128 accumulators, two waves per SIMD; stages of 64 reduction
-// indices through LDS in the planes' own order.  grid: (column blocks x row blocks of this segment, zb); `order` 1 walks the blocks in 4 x 8 groups per XCD,
-// 0 in row runs per XCD, 2 plainly (measured: no difference, tools/bench_i8_gemm.py).
+// indices through LDS in the planes' own order.  grid: (column blocks x row blocks of this segment, zb); the blocks go in 4 x 8 groups per XCD where the
+// grid allows it, plainly otherwise (row runs per XCD were measured too, no difference: tools/bench_i8_gemm.py, round 6; removed).
 // (First version, measured: four waves of 64 x 64 with SIX products, weight <= 2 — 17 ms per 32 x 4096^2, but on rows with a spike over a floor 1e-3
 // below it the floor's values sit in the low digits and the dropped weight-3 products were 2.4e-5 of sigma_1 in U sigma, fifty times the bf16 form.)
 __global__ __launch_bounds__(512) void nn_gemm_i8_kernel(TallBatch tb, const signed char* __restrict__ planesA, int64_t strideA, int rps,
                                                          const signed char* __restrict__ planesB, int64_t strideB, int jps, int cgs,
                                                          const int* __restrict__ aex, int rows_pad, const int* __restrict__ gex, int kp, int r0, int rows, int k,
-                                                         int64_t ldo, int gx, int gy, int order) {
+                                                         int64_t ldo, int gx, int gy) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // 2 x GI_STAGE_BYTES
     const int z = blockIdx.y;
     float* __restrict__ out = tb.lng[z];
@@ -173,15 +173,11 @@ __global__ __launch_bounds__(512) void nn_gemm_i8_kernel(TallBatch tb, const sig
     int Ib, Jb;
     {
         const int total = gx * gy, id = blockIdx.x;
-        if (order == 1 && (total & 7) == 0 && (gx & 7) == 0 && (gy & 3) == 0) {
+        if ((total & 7) == 0 && (gx & 7) == 0 && (gy & 3) == 0) {
             const int lid = (id & 7) * (total >> 3) + (id >> 3);   // consecutive ids of one XCD
             const int g = lid >> 5, wi_ = lid & 31, ggx = gx >> 3;
             Ib = (g / ggx) * 4 + (wi_ >> 3);
             Jb = (g % ggx) * 8 + (wi_ & 7);
-        } else if (order == 0 && (total & 7) == 0) {
-            const int lid = (id & 7) * (total >> 3) + (id >> 3);   // row runs per XCD
-            Ib = lid / gx;
-            Jb = lid % gx;
         } else {
             Ib = id / gx;
             Jb = id % gx;

@@ -34,7 +34,7 @@
 #include <unistd.h>
 
 namespace asvdk {
-thread_local int g_call_cus = 0;   // see call_cus(): set per host thread for the duration of a half-batch call (0: the whole device)
+thread_local int g_call_cus = 0;   // see call_cus_now(): set per host thread for the duration of a half-batch call (0: the whole device)
 // CUs of the current device (hipDeviceAttributeMultiprocessorCount, cached per device).  256 — the MI355X — when no device is visible: the
 // host-side size queries (asvd_svd_worksize) answer on a CPU-only box too.
 int device_cus() {
@@ -60,13 +60,6 @@ using namespace asvdk;
 #include "nn_gemm_i8.h"
 #include "snapshot_i8.h"
 
-// --------------------------------------------------------------------------------------------------
-// ASVD_ORDER=rr: round-robin tournament instead of the XOR pair schedule (A/B measurements; single-level sweeps only)
-static bool pair_order_xor() {
-    const char* e = getenv("ASVD_ORDER");
-    return !(e && !strncmp(e, "rr", 2));
-}
-
 struct Plan {
     int batch;
     int64_t m, n;         // as given
@@ -82,13 +75,11 @@ struct Plan {
     size_t off_x, off_xorig, off_gpart, off_q, off_active, off_sig, off_ina, off_inv, off_perm, off_flags, off_pflag, off_plist, off_snap, off_snapex, total;
 };
 
-// CUs the launches of the current call may use: those of the device (256 on the MI355X), or those of one half when asvd_svd_batched runs a batch
-// as two halves on CU-masked streams (below).  The launch geometry of a plan (row splits, chunk counts) is sized for this many.
-static int64_t call_cus() { return call_cus_now(); }
-
 int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p) {
     if (batch < 1 || m < 1 || n < 1 || m > (1 << 24) || n > (1 << 24)) return ASVD_E_BADARG;
-    const int64_t cu = call_cus();
+    // CUs the launches of the current call may use: those of the device (256 on the MI355X), or those of one half when asvd_svd_batched runs a
+    // batch as two halves on CU-masked streams (below).  The launch geometry of a plan (row splits, chunk counts) is sized for this many.
+    const int64_t cu = call_cus_now();
     p.batch = batch;
     p.m = m;
     p.n = n;
@@ -101,7 +92,7 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
     {
         int pw2 = 2;
         while (pw2 < p.nb) pw2 <<= 1;
-        p.npairs = pair_order_xor() ? pw2 / 2 : p.nb / 2;  // XOR ordering runs over the panel count padded to a power of two
+        p.npairs = pw2 / 2;  // XOR ordering runs over the panel count padded to a power of two
     }
     // want_u / want_vv: left / right vectors OF THE ORIENTED problem (columns of the rotated matrix / backsolved V rows)
     p.want_v = (want_u || want_vv) ? 1 : 0;
@@ -111,12 +102,11 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
     // gram: choose the row split that minimises (rounds of resident workgroups) x (chunks per wave + fixed overhead).
     // 3 workgroups of 4 waves fit per CU (148 VGPR+AGPR) -> 768 slots; a grid of 1.3 x slots costs 2 full rounds.
     {
-        const int launch_batch = batch;  // problems per launch
         const int64_t nchunk_total = p.m_pad / 32;
         int64_t best_ns = 1;
         double best_cost = 1e300;
         for (int64_t ns = 1; ns <= nchunk_total && ns <= 64; ++ns) {
-            const int64_t wgs = ns * p.npairs * launch_batch;
+            const int64_t wgs = ns * p.npairs * batch;
             const int64_t rounds = ceil_div64(wgs, 3 * cu);
             const int64_t chunks_wg = ceil_div64(nchunk_total, ns);
             const int64_t chunks_wave = ceil_div64(chunks_wg, 4);
@@ -133,20 +123,18 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
     p.rows_per_wg = (int)(ceil_div64(iters_total, nc) * 128);
     p.nchunks = (int)ceil_div64(p.R_upd, p.rows_per_wg);
     {
-        // two-level dense sweeps: default for >= 8 panels under the XOR ordering (ASVD_TWOLEVEL=0 restores the single-level sweep)
-        const char* e2 = getenv("ASVD_TWOLEVEL");
-        p.two = (pair_order_xor() && p.nb >= 8 && !(e2 && atoi(e2) == 0)) ? 1 : 0;
+        // two-level dense sweeps for >= 8 panels; smaller problems run the single-level sweep
+        p.two = p.nb >= 8 ? 1 : 0;
         p.ns = p.nb / 2;
         int pw2 = 2;
         while (pw2 < p.ns) pw2 <<= 1;
         p.npairs_s = pw2 / 2;
-        const int launch_batch = batch;
         // sgram6: 3 workgroups (32 KiB LDS, ~150 VGPRs) per CU -> 768 slots; 16-row chunks per wave, same cost model as the single-level Gram
         const int64_t nchunk_total = p.m_pad / 32;
         int64_t best_ns = 1;
         double best_cost = 1e300;
         for (int64_t ns = 1; ns <= nchunk_total && ns <= 64; ++ns) {
-            const int64_t wgs = ns * p.npairs_s * launch_batch;
+            const int64_t wgs = ns * p.npairs_s * batch;
             const int64_t rounds = ceil_div64(wgs, 3 * cu);
             const int64_t chunks_wave = ceil_div64(2 * ceil_div64(nchunk_total, ns), 4);
             const double cost = (double)rounds * ((double)chunks_wave + 1.5) + 0.02 * ns;
@@ -156,7 +144,7 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
         p.nsplit_s = (int)ceil_div64(p.m_pad, p.rows_per_split_s);
         // supdate: 32-row tiles; aim for >= 1024 workgroups per launch and >= 4 tiles per workgroup
         const int64_t tiles = ceil_div64(p.R_upd, 32);
-        int64_t wantc = ceil_div64(4 * cu, (int64_t)p.npairs_s * launch_batch);
+        int64_t wantc = ceil_div64(4 * cu, (int64_t)p.npairs_s * batch);
         int64_t nc = std::max<int64_t>(1, std::min<int64_t>(wantc, ceil_div64(tiles, 4)));
         p.rows_per_wg_s = (int)(ceil_div64(tiles, nc) * 32);
         p.nchunks_s = (int)ceil_div64(p.R_upd, p.rows_per_wg_s);
@@ -338,6 +326,22 @@ int launch_pack(const void* src, int64_t ld, const void* s, int cs_dtype, const 
     return ASVD_OK;
 }
 
+// every problem of the batch into its panels (p.batch_stride floats per problem from X on)
+int pack_batch(const void* const* a_host, int a_dtype, int64_t lda, const void* const* cs_host, int cs_dtype, const Plan& p, float* X, hipStream_t st) {
+    for (int b = 0; b < p.batch; ++b) {
+        float* Xb = X + (int64_t)b * p.batch_stride;
+        const void* s = cs_host ? cs_host[b] : nullptr;
+        int prc;
+        switch (a_dtype) {
+            case ASVD_F32: prc = launch_pack<ASVD_F32>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
+            case ASVD_F16: prc = launch_pack<ASVD_F16>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
+            default: prc = launch_pack<ASVD_BF16>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
+        }
+        if (prc) return prc;
+    }
+    return ASVD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,7 +386,7 @@ int asvd_svd_get_profile(float* ms_host, int* launches_host) {
 static bool tall_wanted(const Plan& p);
 static size_t tall_worksize(int batch, int64_t m, int64_t n, int want_vectors, int64_t k);
 
-// workspace of ONE call of `batch` problems whose launches are sized for the CUs of the current thread (call_cus())
+// workspace of ONE call of `batch` problems whose launches are sized for the CUs of the current thread (call_cus_now())
 static int worksize_one(int batch, int64_t m, int64_t n, int want_vectors, size_t* bytes) {
     Plan p;
     int rc = make_plan(batch, m, n, want_vectors, want_vectors, p);
@@ -557,6 +561,64 @@ int asvd_svd_worksize(int batch, int64_t m, int64_t n, int want_vectors, size_t*
     return ASVD_OK;
 }
 
+// Sparse sweeps: marks -> lists of disjoint pairs.  The pairs of one XOR step (I ^ J == d) are disjoint by construction, but late in the
+// iteration a step holds a handful of pairs and a sweep of nb-1 three-launch steps is all launch latency.  The marked pairs of every running
+// problem (flags: [batch][nb][nb], host_done: [batch]) are therefore packed first-fit, in schedule order (step, then I), into at most nsteps
+// ROUNDS whose pairs share no panel (per problem: a bitmask of used panels per round); a round is launched like a step.  Any order of disjoint
+// rotations is a valid Jacobi sweep; first-fit keeps the nearest-neighbour-first order of the XOR schedule among conflicting pairs.
+// list: cnt[r] slots per problem for round r from off[r] on (code I << 16 | J, -1 = empty slot).  Returns the number of marked pairs.
+static long long pack_marked_pairs(const std::vector<unsigned char>& flags, const std::vector<int>& host_done, int nb, int nsteps,
+                                   std::vector<int>& list, std::vector<int>& off, std::vector<int>& cnt) {
+    const int batch = (int)host_done.size();
+    long long marked_total = 0;
+    list.clear();
+    std::vector<std::vector<int>> tmp((size_t)batch * nsteps);  // [b * nsteps + round]
+    const int words = (nb + 63) / 64;
+    std::vector<uint64_t> used;  // [round][words] of the problem being packed
+    for (int b = 0; b < batch; ++b) {
+        if (host_done[b]) continue;
+        const unsigned char* f = flags.data() + (size_t)b * nb * nb;
+        bool packed = true;
+        used.assign((size_t)nsteps * words, 0);
+        long long n = 0;
+        for (int d = 1; d <= nsteps && packed; ++d)
+            for (int I = 0; I < nb && packed; ++I) {
+                const int J = I ^ d;
+                if (J <= I || J >= nb || !f[(size_t)I * nb + J]) continue;
+                int r = 0;
+                for (; r < nsteps; ++r) {
+                    uint64_t* u = &used[(size_t)r * words];
+                    if (!((u[I >> 6] >> (I & 63)) & 1) && !((u[J >> 6] >> (J & 63)) & 1)) {
+                        u[I >> 6] |= 1ull << (I & 63);
+                        u[J >> 6] |= 1ull << (J & 63);
+                        break;
+                    }
+                }
+                if (r == nsteps) { packed = false; break; }  // cannot happen below ~nsteps/2 marks per panel; fall back
+                tmp[(size_t)b * nsteps + r].push_back((I << 16) | J);
+                ++n;
+            }
+        if (packed) marked_total += n;
+        else {  // one list per XOR step
+            for (int r = 0; r < nsteps; ++r) tmp[(size_t)b * nsteps + r].clear();
+            for (int I = 0; I < nb; ++I)
+                for (int J = I + 1; J < nb; ++J)
+                    if (f[(size_t)I * nb + J]) { tmp[(size_t)b * nsteps + ((I ^ J) - 1)].push_back((I << 16) | J); ++marked_total; }
+        }
+    }
+    for (int r = 0; r < nsteps; ++r) {
+        size_t mx = 0;
+        for (int b = 0; b < batch; ++b) mx = std::max(mx, tmp[(size_t)b * nsteps + r].size());
+        cnt[r] = (int)mx;
+        off[r] = (int)list.size();
+        for (int b = 0; b < batch; ++b) {
+            const auto& v = tmp[(size_t)b * nsteps + r];
+            for (size_t i = 0; i < mx; ++i) list.push_back(i < v.size() ? v[i] : -1);
+        }
+    }
+    return marked_total;
+}
+
 // allow_f16: the fused update + Gram kernel of the dense sweeps (split-fp16 arithmetic with power-of-two column scales taken from the carried
 // column norms, twolevel.h).  *retry_plain is set, and nothing is finalised, when a problem turned NaN on that path: the caller then repeats the
 // call with the separate passes (fp32 Gram pass, split-bf16 update pass), which need no scales — a NaN that is in the data comes back as NaN.
@@ -604,17 +666,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
         ProfScope ps(0, st);
         ASVD_HIP_CHECK(hipMemsetAsync(X, 0, (size_t)p.batch_stride * batch * sizeof(float), st));
         ASVD_HIP_CHECK(hipMemsetAsync(wb + p.off_flags, 0, (size_t)batch * 4 * sizeof(int), st));
-        for (int b = 0; b < batch; ++b) {
-            float* Xb = X + (int64_t)b * p.batch_stride;
-            const void* s = cs_host ? cs_host[b] : nullptr;
-            int prc;
-            switch (a_dtype) {
-                case ASVD_F32: prc = launch_pack<ASVD_F32>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
-                case ASVD_F16: prc = launch_pack<ASVD_F16>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
-                default: prc = launch_pack<ASVD_BF16>(a_host[b], lda, s, cs_dtype, p, Xb, st); break;
-            }
-            if (prc) return prc;
-        }
+        if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, X, st)) return prc;
         if (p.vmode == 2) {
             // keep the packed original (A rows of every panel) for the final backsolve
             ASVD_HIP_CHECK(hipMemcpy2DAsync(wb + p.off_xorig, (size_t)p.m_pad * PB * sizeof(float), X, (size_t)p.R * PB * sizeof(float),
@@ -630,14 +682,13 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
     const bool debug = getenv("ASVD_DEBUG") != nullptr;
     // the call's schedule description: a kernel argument of every launch below (no process-global device state)
     Sched sc = default_sched();
-    sc.pair_order = pair_order_xor() ? 1 : 0;
     sc.super_order = super_grouped_for(p) ? 2 : 1;
     if (sc.super_order == 2) set_group_table(sc, p.ns, group_bits_for(p.ns));
-    const int nsteps = pair_order_xor() ? 2 * p.npairs - 1 : p.nb - 1;
+    const int nsteps = 2 * p.npairs - 1;
     // panels whose convergence is enforced: those holding the k leading columns, plus one panel of margin
     const int kb = (int)(ceil_div64(k, PB) + 1 < p.nb ? ceil_div64(k, PB) + 1 : p.nb);
     // one inner sweep of the 64x64 eigen-solve per visit: with the XOR schedule a second one no longer saves outer sweeps
-    // (measured 26.3 vs 25.9 SVD/s; under the round-robin order two inner sweeps cut 15 -> 13 outer sweeps)
+    // (measured 26.3 vs 25.9 SVD/s)
     constexpr int inner_sweeps = 1;
     int sweep = 0;
     // Step schedule of a single-level dense sweep (XOR distances d, stored as step = d-1).  The local levels d = 1..L are run twice at the
@@ -646,7 +697,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
     std::vector<int> sched;
     {
         const int P2 = nsteps + 1;
-        const int L = pair_order_xor() ? std::min(std::max(0, std::min(7, P2 / 16 - 1)), nsteps) : 0;
+        const int L = std::min(std::max(0, std::min(7, P2 / 16 - 1)), nsteps);
         for (int d = 1; d <= L; ++d) sched.push_back(d - 1);
         for (int st2 = 0; st2 < nsteps; ++st2) sched.push_back(st2);
     }
@@ -654,20 +705,18 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
     unsigned char* pflag = (unsigned char*)(wb + p.off_pflag);
     int* plist_dev = (int*)(wb + p.off_plist);
     float* dnorm = (float*)(wb + p.off_ina);  // squared column norms of the snapshot (finalize overwrites this buffer later)
-    const bool sparse_allowed = pair_order_xor() && p.nb >= 8 && !(getenv("ASVD_SPARSE") && atoi(getenv("ASVD_SPARSE")) == 0);
+    const bool sparse_allowed = p.nb >= 8;
     constexpr double sparse_frac = 0.5;
     bool sparse = false;
     std::vector<unsigned char> hflag;
     std::vector<int> hlist;
     std::vector<int> sl_off((size_t)(nsteps > 0 ? nsteps : 1), 0), sl_cnt((size_t)(nsteps > 0 ? nsteps : 1), 0);
     bool fused_used = false;
-    int* hist_dev = nullptr;
-    if (getenv("ASVD_DEBUG_HIST")) { ASVD_HIP_CHECK(hipMalloc(&hist_dev, 10 * sizeof(int))); }
-    // every exit of this function — the ASVD_HIP_CHECK returns included — frees the debug histogram and closes the profile it opened
+    // every exit of this function — the ASVD_HIP_CHECK returns included — closes the profile it opened
     struct ExitGuard {
-        int*& hist; bool prof;
-        ~ExitGuard() { if (hist) { (void)hipFree(hist); hist = nullptr; } if (prof) prof_end(); }
-    } exit_guard{hist_dev, g_prof_enabled && manage_profile};
+        bool prof;
+        ~ExitGuard() { if (prof) prof_end(); }
+    } exit_guard{g_prof_enabled && manage_profile};
     // buffers of the two-level sweeps as the kernels see them
     EvdV3 v3{};
     v3.ns = p.ns;
@@ -678,11 +727,9 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
     v3.Qfin = (float*)(wb + p.off_qfin);
     v3.subact = (int*)(wb + p.off_subact);
     v3.Din = (float*)(wb + p.off_din);
-    v3.hist = hist_dev;
     float* Gx6 = (float*)(wb + p.off_gx6);
     for (; sweep < max_sweeps; ++sweep) {
         const auto sweep_t0 = std::chrono::steady_clock::now();
-        if (hist_dev) ASVD_HIP_CHECK(hipMemsetAsync(hist_dev, 0, 10 * sizeof(int), st));
         ASVD_HIP_CHECK(hipMemsetAsync(maxoff, 0, (size_t)batch * sizeof(int), st));
         ASVD_HIP_CHECK(hipMemsetAsync(nrot, 0, (size_t)batch * sizeof(int), st));
         ASVD_HIP_CHECK(hipMemsetAsync(nupd, 0, (size_t)batch * sizeof(int), st));
@@ -717,57 +764,8 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
             ASVD_HIP_CHECK(hipMemcpyAsync(hflag.data(), pflag, hflag.size(), hipMemcpyDeviceToHost, st));
             ASVD_HIP_CHECK(hipStreamSynchronize(st));
             if (debug) fprintf(stderr, "[asvd_svd]   snapshot + readback %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count());
-            // 2. marks -> lists of disjoint pairs.  The pairs of one XOR step (I ^ J == d) are disjoint by construction, but late in the
-            // iteration a step holds a handful of pairs and a sweep of nb-1 three-launch steps is all launch latency.  The marked
-            // pairs are therefore packed first-fit, in schedule order (step, then I), into ROUNDS whose pairs share no panel (per
-            // problem: a bitmask of used panels per round); a round is launched like a step.  Any order of disjoint rotations is a
-            // valid Jacobi sweep; first-fit keeps the nearest-neighbour-first order of the XOR schedule among conflicting pairs.
-            // (The list slots are indexed by `step` below.)
-            hlist.clear();
-            std::vector<std::vector<int>> tmp((size_t)batch * nsteps);  // [b * nsteps + round]
-            const int words = (p.nb + 63) / 64;
-            std::vector<uint64_t> used;  // [round][words] of the problem being packed
-            for (int b = 0; b < batch; ++b) {
-                if (host_done[b]) continue;
-                const unsigned char* f = hflag.data() + (size_t)b * p.nb * p.nb;
-                bool packed = true;
-                used.assign((size_t)nsteps * words, 0);
-                long long cnt = 0;
-                for (int d = 1; d <= nsteps && packed; ++d)
-                    for (int I = 0; I < p.nb && packed; ++I) {
-                        const int J = I ^ d;
-                        if (J <= I || J >= p.nb || !f[(size_t)I * p.nb + J]) continue;
-                        int r = 0;
-                        for (; r < nsteps; ++r) {
-                            uint64_t* u = &used[(size_t)r * words];
-                            if (!((u[I >> 6] >> (I & 63)) & 1) && !((u[J >> 6] >> (J & 63)) & 1)) {
-                                u[I >> 6] |= 1ull << (I & 63);
-                                u[J >> 6] |= 1ull << (J & 63);
-                                break;
-                            }
-                        }
-                        if (r == nsteps) { packed = false; break; }  // cannot happen below ~nsteps/2 marks per panel; fall back
-                        tmp[(size_t)b * nsteps + r].push_back((I << 16) | J);
-                        ++cnt;
-                    }
-                if (packed) marked_total += cnt;
-                else {  // one list per XOR step
-                    for (int r = 0; r < nsteps; ++r) tmp[(size_t)b * nsteps + r].clear();
-                    for (int I = 0; I < p.nb; ++I)
-                        for (int J = I + 1; J < p.nb; ++J)
-                            if (f[(size_t)I * p.nb + J]) { tmp[(size_t)b * nsteps + ((I ^ J) - 1)].push_back((I << 16) | J); ++marked_total; }
-                }
-            }
-            for (int step = 0; step < nsteps; ++step) {
-                size_t mx = 0;
-                for (int b = 0; b < batch; ++b) mx = std::max(mx, tmp[(size_t)b * nsteps + step].size());
-                sl_cnt[step] = (int)mx;
-                sl_off[step] = (int)hlist.size();
-                for (int b = 0; b < batch; ++b) {
-                    const auto& v = tmp[(size_t)b * nsteps + step];
-                    for (size_t i = 0; i < mx; ++i) hlist.push_back(i < v.size() ? v[i] : -1);
-                }
-            }
+            // 2. marks -> lists of disjoint pairs
+            marked_total = pack_marked_pairs(hflag, host_done, p.nb, nsteps, hlist, sl_off, sl_cnt);
             if (debug) fprintf(stderr, "[asvd_svd]   lists built at %.2f ms (%zu slots)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count(), hlist.size());
             if (!hlist.empty()) ASVD_HIP_CHECK(hipMemcpyAsync(plist_dev, hlist.data(), hlist.size() * sizeof(int), hipMemcpyHostToDevice, st));
         }
@@ -783,13 +781,13 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
                 const int* pl = plist_dev + sl_off[step];
                 // few pairs per launch: split the rows further to fill the CUs, within the partial-Gram capacity of a problem
                 const int64_t chunks = p.m_pad / 32, cap = (int64_t)p.npairs * p.nsplit / slots;
-                int64_t ns = std::max<int64_t>(p.nsplit, ceil_div64(3 * call_cus(), (int64_t)slots * batch));
+                int64_t ns = std::max<int64_t>(p.nsplit, ceil_div64(3 * call_cus_now(), (int64_t)slots * batch));
                 ns = std::min<int64_t>(std::min<int64_t>(ns, cap), std::min<int64_t>(chunks, 64));
                 if (ns < 1) ns = 1;
                 const int rps = (int)(ceil_div64(chunks, ns) * 32);
                 const int nsp = (int)ceil_div64(p.m_pad, rps);
                 const int64_t iters = ceil_div64(p.R_upd, 128);
-                int64_t nc = std::min<int64_t>(iters, std::max<int64_t>(1, ceil_div64(4 * call_cus(), (int64_t)slots * batch)));
+                int64_t nc = std::min<int64_t>(iters, std::max<int64_t>(1, ceil_div64(4 * call_cus_now(), (int64_t)slots * batch)));
                 const int rpw = (int)(ceil_div64(iters, nc) * 128);
                 const int nch = (int)ceil_div64(p.R_upd, rpw);
                 {
@@ -798,9 +796,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
                 }
                 {
                     ProfScope ps(2, st);
-                    EvdV3 none{};
-                    none.hist = hist_dev;
-                    launch_evdw0(false, slots, batch, st, sc, Gpart, nsp, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, pl, slots, none);
+                    launch_evdw0(false, slots, batch, st, sc, Gpart, nsp, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, pl, slots, EvdV3{});
                 }
                 {
                     ProfScope ps(7, st);
@@ -818,9 +814,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
                 if (two_now) {  // internal step: also emits the fresh carried diagonal blocks of both panels of every pair
                     launch_evdw0(true, p.npairs, batch, st, sc, Gpart, p.nsplit, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, nullptr, 0, v3);
                 } else {
-                    EvdV3 none{};
-                    none.hist = hist_dev;
-                    launch_evdw0(false, p.npairs, batch, st, sc, Gpart, p.nsplit, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, nullptr, 0, none);
+                    launch_evdw0(false, p.npairs, batch, st, sc, Gpart, p.nsplit, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, nullptr, 0, EvdV3{});
                 }
             }
             {
@@ -844,31 +838,11 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
             // which reads every panel of a quad with a present member, loses to the separate passes, which touch only the pairs that exist
             // (13B shapes, ns = 80 in a 128-wide schedule: always fused 21.4 s, never fused 16.9 s for the model): fused on full schedules only
             const bool ns_pow2 = (p.ns & (p.ns - 1)) == 0;
-            // ASVD_SPREAD_FROM=<k> (measurement knob, XOR schedules over 4^j super-panels only): from dense sweep k (0-based) on, the XOR
-            // distances run in LINE-SPREAD order — triples {d, w(d), w^2(d)}, w: base-4 digits 1 -> 2 -> 3 -> 1, which XOR to zero, so that the
-            // four super-panels {a, a^D, a^E, a^D^E} of a quad are closed under all three steps of a triple (what a
-            // three-steps-per-pass kernel would need).  Any order of the distances is a valid sweep; this one gives up nearest-neighbour-first.
-            std::vector<int> dist(nsuper);
-            for (int di = 0; di < nsuper; ++di) dist[di] = di + 1;
-            {
-                const char* es = getenv("ASVD_SPREAD_FROM");
-                int lg = 0;
-                while ((1 << lg) < p.ns) ++lg;
-                if (es && !super_grp && ns_pow2 && (lg % 2) == 0 && sweep >= atoi(es)) {
-                    auto w = [](int d) { int o = 0; for (int sh = 0; sh < 30; sh += 2) { const int g = (d >> sh) & 3; o |= (g == 0 ? 0 : (g == 1 ? 2 : (g == 2 ? 3 : 1))) << sh; } return o; };
-                    std::vector<char> used(p.ns, 0);
-                    int at = 0;
-                    for (int d = 1; d < p.ns; ++d) {
-                        if (used[d]) continue;
-                        const int d2 = w(d), d3 = w(d2);
-                        used[d] = used[d2] = used[d3] = 1;
-                        dist[at++] = d; dist[at++] = d2; dist[at++] = d3;
-                    }
-                }
-            }
+            // (Round 5 measured a LINE-SPREAD order of the distances from a given dense sweep on — triples {d, w(d), w^2(d)} that close the four
+            // super-panels of a quad — against this one: slower from every starting sweep, profiles/r5_spread_order_from_sweep.txt; removed.)
             for (int di = 0; di < nsuper; ++di) {
-                const int D = dist[di];
-                const int E = (di + 1 < nsuper) ? dist[di + 1] : 0;  // 0: last super-step of the sweep
+                const int D = di + 1;
+                const int E = (di + 1 < nsuper) ? di + 2 : 0;  // 0: last super-step of the sweep
                 auto fused_after = [&](int dj) {  // does the launch of super-step index dj also leave the tiles of index dj + 1 ?
                     if (!fuse_ug || dj < 0 || dj + 1 >= nsuper) return false;
                     if (super_grp) {  // consecutive steps inside the groups (XOR distances 1..15), or consecutive offsets of the same round of group pairs
@@ -879,8 +853,6 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
                 };
                 const bool gram_in = !fused_after(di - 1);   // tiles of this step not left by the previous launch
                 const bool gram_out = fused_after(di);
-                const int gx_slots = std::max(p.nsplit_s, p.nchunks_q);  // partial-tile slots per super-pair in the buffer
-                (void)gx_slots;
                 v3.nsplit6 = gram_in ? p.nsplit_s : p.nchunks_q;
                 v3.Gx6 = Gx6;
                 if (gram_in) {
@@ -889,7 +861,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
                 }
                 {
                     ProfScope ps(2, st);  // both inner steps of every super-pair in one launch, one wave per 64x64 solve (evd_wave.hip)
-                    launch_evdw12(p.npairs_s, batch, st, sc, maxoff, nrot, done, tol, inner_sweeps, p.nb, D - 1, kb, v3, sweep, p.cols >= 2048 ? 2 : 0);
+                    launch_evdw12(p.npairs_s, batch, st, sc, maxoff, nrot, done, tol, inner_sweeps, p.nb, D - 1, kb, v3, p.cols >= 2048);
                 }
                 {
                     ProfScope ps(gram_out ? 8 : 3, st);
@@ -904,13 +876,6 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
         }
         ASVD_HIP_CHECK(hipMemcpyAsync(flags.data(), wb + p.off_flags, (size_t)batch * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
         ASVD_HIP_CHECK(hipStreamSynchronize(st));
-        if (hist_dev) {
-            int hh[10];
-            ASVD_HIP_CHECK(hipMemcpy(hh, hist_dev, sizeof(hh), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[asvd_svd] sweep %d pair-measure histogram by decade 1e0..1e-9:", sweep + 1);
-            for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", hh[i]);
-            fprintf(stderr, "\n");
-        }
         if (g_prof_enabled) {
             long long rot = 0;
             for (int b = 0; b < batch; ++b) rot += host_done[b] ? 0 : flags[batch + b];
@@ -977,8 +942,7 @@ static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int
             backsolve_kernel<<<dim3((unsigned)ceil_div64(p.nb, 4), (unsigned)ceil_div64(p.nb, 4), batch), 256, 0, st>>>(
                 (const float*)(wb + p.off_xorig), ops, ops * p.nb, X, p.panel_stride, p.batch_stride, p.nb, p.m_pad);
         }
-        colnorm_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(X, p.panel_stride, p.batch_stride, p.m_pad, p.R, p.n_pad,
-                                                          p.vmode == 1 ? 1 : 0, sig, ina, inv);
+        colnorm_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(X, p.panel_stride, p.batch_stride, p.m_pad, p.R, p.n_pad, sig, ina, inv);
         rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(sig, p.n_pad, perm);
         for (int b = 0; b < batch; ++b) {
             float* Uo = U_host ? U_host[b] : nullptr;
@@ -1061,7 +1025,6 @@ static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_s
     const int seg = (int)round_up64(ceil_div64(m64, nseg), 64);
     ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)gram_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
     const int nt = (nb + 3) / 4, ntri = nt * (nt + 1) / 2;
-    const int order = getenv("ASVD_GI_ORDER") ? atoi(getenv("ASVD_GI_ORDER")) : 0;   // measurement knob (block order of gram_i8_kernel)
     for (int s = 0; s < nseg; ++s) {
         const int r0 = s * seg;
         const int rows = (int)std::min<int64_t>(seg, m64 - r0);
@@ -1071,7 +1034,7 @@ static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_s
         split_i8_kernel<<<dim3(nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(Xp, panel_stride, batch_stride, nb, m_pad, n_pad, ex, r0, kgs,
                                                                                        scratch, plane_stride, inv, nullptr);
         gram_i8_kernel<<<dim3(ntri, batch), 512, 2 * GI_STAGE_BYTES, st>>>(scratch, plane_stride, nb, kgs, n_pad, inv ? exs : ex, G, ldg, gbs, s > 0 ? 1 : 0, nt,
-                                                                           dp, order);
+                                                                           dp);
     }
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
@@ -1160,17 +1123,7 @@ static int svd_tall(int batch, const void* const* a_host, int a_dtype, int64_t m
         ProfScope ps(0, st);
         ASVD_HIP_CHECK(hipMemsetAsync(Xp, 0, (size_t)p.batch_stride * batch * sizeof(float), st));
         ASVD_HIP_CHECK(hipMemsetAsync(fail, 0, (size_t)batch * sizeof(int), st));
-        for (int b = 0; b < batch; ++b) {
-            float* Xb = Xp + (int64_t)b * p.batch_stride;
-            const void* sc = cs_host ? cs_host[b] : nullptr;
-            int prc;
-            switch (a_dtype) {
-                case ASVD_F32: prc = launch_pack<ASVD_F32>(a_host[b], lda, sc, cs_dtype, p, Xb, st); break;
-                case ASVD_F16: prc = launch_pack<ASVD_F16>(a_host[b], lda, sc, cs_dtype, p, Xb, st); break;
-                default: prc = launch_pack<ASVD_BF16>(a_host[b], lda, sc, cs_dtype, p, Xb, st); break;
-            }
-            if (prc) return prc;
-        }
+        if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, Xp, st)) return prc;
         // G = X^T X: exact integer arithmetic on the int8 matrix pipe (gram_i8.h), or the fp64 matrix instructions (ASVD_GRAM_I8=0), then
         // sort columns by decreasing norm (stable, padding last; 14 -> 10 sweeps, unsorted saves nothing), permute + unit-scale the Gram matrix.
         // The int8 path takes the norms from the data first (fp64, colmaxexp_kernel) and stores the sorted, scaled matrix directly: Gs = D^-1 P^T G~ P D^-1
@@ -1210,8 +1163,7 @@ static int svd_tall(int batch, const void* const* a_host, int a_dtype, int64_t m
         // of group g's trailing update, the next group's strip updated first.  Reduction 48.1-48.5 -> 52.3 ms per 32 x 4096^2: the two extra launches and
         // event hand-overs per group cost more than the 0.5 ms chain they hide, and the trailing update loses the CUs the chain occupies.)
         // (block rows per group, 32 x 4096^2, reduction ms: 2: 48.0 · 4: 44.4-44.6 · 5: 42.1 · 6: 42.2-42.6 · 7: 41.9 · 8: 44.9-45.2 — profiles/r6_chol_group.txt)
-        int cg = 6;
-        if (const char* ecg = getenv("ASVD_CHOL_GROUP")) cg = std::max(1, std::min(16, atoi(ecg)));   // measurement knob: block rows per grouped trailing update
+        constexpr int cg = 6;
         for (int j0 = 0; j0 < nbk; j0 += cg) {
             const int j1 = std::min(nbk, j0 + cg);
             for (int jb = j0; jb < j1; ++jb) {
@@ -1308,8 +1260,7 @@ static int svd_tall(int batch, const void* const* a_host, int a_dtype, int64_t m
                                                                                                   aex, (int)r0, cgs, planesA, strideA);
                     const int gx = (int)ceil_div64(jps, 4), gy = (int)ceil_div64(rps, 4);
                     nn_gemm_i8_kernel<<<dim3(gx * gy, zb), 512, 2 * GI_STAGE_BYTES, st>>>(tb, planesA, strideA, rps, planesB, strideB, jps, cgs, aex, rows_pad, gex, kp,
-                                                                                         (int)r0, p.rows, (int)k, k, gx, gy,
-                                                                                         getenv("ASVD_NI_ORDER") ? atoi(getenv("ASVD_NI_ORDER")) : 1);
+                                                                                         (int)r0, p.rows, (int)k, k, gx, gy);
                 }
             } else {
                 nn_gemm_split_kernel<<<dim3((unsigned)ceil_div64(k, 128), (unsigned)ceil_div64(p.rows, 128), zb), 256, 0, st>>>(

@@ -143,16 +143,12 @@ int asvd_scale_cols(const void* w, int w_dtype, int64_t m, int64_t n, int64_t ld
  * uses scratch.  tests/test_gpu_concurrency.py holds the library to it (two threads x 8 x 4096^2 next to a stream of foreign
  * GEMMs, and calls with different pair schedules side by side: bit-identical results and sweep counts against serial runs).
  * Environment (read on the host, all optional; none changes results beyond rounding): ASVD_DEBUG (trace on stderr),
- * ASVD_DEBUG_HIST (pair-measure histogram per sweep), ASVD_ORDER=rr (round-robin instead of XOR pair order, single-level sweeps),
- * ASVD_TWOLEVEL=0, ASVD_SUPGRAM=0 (separate Gram / update passes), ASVD_SPARSE=0, ASVD_NO_REDUCE (skip the Cholesky-QR),
- * ASVD_EVDQ=0/1 (force the throughput / latency form of the eigen-solver), ASVD_EVDW_TRACE (stage stamps of the solver),
- * ASVD_SPREAD_FROM=<sweep> (line-spread order of the XOR distances from that dense sweep on: a measurement knob),
- * ASVD_SPLIT=0 (never split a batch over the two halves of the chip), ASVD_RING=0/1/2 + ASVD_RING_FROM=<sweep> (cross-only ring visits of the
- * eigen-solves: off / both inner steps / inner step 1 only — the default for >= 2048 columns is 2), ASVD_GRAM_I8=0 (Gram matrix of the reduction
- * with the fp64 matrix instructions instead of the exact int8 digit products, csrc/gram_i8.h), ASVD_NN_I8=0 (long-side product X V with six bf16
- * products per fp32 product instead of the int8 fixed-point form, csrc/nn_gemm_i8.h), ASVD_SNAP_I8=0 (coupling snapshot of the sparse sweeps with
- * three fp16 products per fp32 product instead of int8 digit planes, csrc/snapshot_i8.h); ASVD_GI_ORDER / ASVD_NI_ORDER=0/1/2 (block order of the two
- * int8 GEMM kernels: measurement knobs, tools/bench_i8_gemm.py).
+ * ASVD_SUPGRAM=0 (separate Gram / update passes), ASVD_NO_REDUCE (skip the Cholesky-QR), ASVD_EVDQ=0/1 (force the throughput / latency form of
+ * the eigen-solver), ASVD_SPLIT=0 (never split a batch over the two halves of the chip), ASVD_RING=2 (cross-only ring visit of inner step 1 of
+ * the eigen-solves below 2048 columns too; the default from 2048 columns on), ASVD_GRAM_I8=0 (Gram matrix of the reduction with the fp64 matrix
+ * instructions instead of the exact int8 digit products, csrc/gram_i8.h), ASVD_NN_I8=0 (long-side product X V with six bf16 products per fp32
+ * product instead of the int8 fixed-point form, csrc/nn_gemm_i8.h), ASVD_SNAP_I8=0 (coupling snapshot of the sparse sweeps with three fp16
+ * products per fp32 product instead of int8 digit planes, csrc/snapshot_i8.h).
  * Returns worst status over the batch.
  */
 int asvd_svd_worksize(int batch, int64_t m, int64_t n, int want_vectors, size_t* bytes);

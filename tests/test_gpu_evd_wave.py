@@ -199,14 +199,15 @@ def test_ring_visit_meets_every_cross_pair_once_and_follows_the_fp64_emulation(g
 
 @pytest.mark.parametrize("n,batch", [(768, 3), (2048, 2)])
 def test_ring_visits_whole_svd_parity_and_forms_bit_identical(gpu, tmp_path, n, batch):
-    """ASVD_RING=1: the two-level sweeps visit their sub-pairs cross-only.  The SVD must still meet the contract against LAPACK, and the wave-local and
-    the cooperative form of the ring visit must agree bit for bit (ASVD_EVDQ=0 / 1)."""
+    """ASVD_RING=2: the two-level sweeps visit the sub-pairs of inner step 1 cross-only (at 768 columns where the size rule would not; at 2048 the
+    default).  The SVD must still meet the contract against LAPACK, and the wave-local and the cooperative form of the ring visit must agree bit
+    for bit (ASVD_EVDQ=0 / 1)."""
     import subprocess
     import sys
     res = {}
     for mode in ("0", "1"):
         out = str(tmp_path / f"ring_evdq{mode}.npz")
-        env = dict(os.environ, ASVD_EVDQ=mode, ASVD_RING="1")
+        env = dict(os.environ, ASVD_EVDQ=mode, ASVD_RING="2")
         subprocess.run([sys.executable, "-c", _COOP_SNIPPET.format(root=ROOT, n=n, batch=batch, out=out)], check=True, env=env, timeout=600)
         res[mode] = np.load(out)
     assert (res["0"]["status"] == 0).all() and np.array_equal(res["0"]["sweeps"], res["1"]["sweeps"])

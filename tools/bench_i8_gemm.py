@@ -1,7 +1,7 @@
 """Micro-benchmark of the int8 matrix-pipe kernels of round 6 (csrc/gram_i8.h, csrc/nn_gemm_i8.h) at the bench shape, 32 x 4096^2:
-the Gram matrix of the reduction alone through the test hook (fp64 matrix instructions / int8 digit path, block orders 0 / 1 / 2), and the
-reduction ("pack") and finalize classes of whole profiled asvd_svd_batched calls with the long-side product on either pipe.
-One JSON object per line.  Knobs: ASVD_GI_ORDER / ASVD_NI_ORDER (measurement only), ASVD_GRAM_I8, ASVD_NN_I8."""
+the Gram matrix of the reduction alone through the test hook (fp64 matrix instructions / int8 digit path), and the reduction ("pack") and
+finalize classes of whole profiled asvd_svd_batched calls with the Gram matrix and the long-side product on either pipe.
+One JSON object per line.  Knobs: ASVD_GRAM_I8, ASVD_NN_I8."""
 import ctypes, json, os, sys
 import torch
 
@@ -37,12 +37,9 @@ def main():
     ex = torch.zeros(batch, n, dtype=torch.int32, device=dev)
     ops_per = 9 * 2 * (n * n * m / 2) * batch
     out = {"what": "gram", "batch": batch, "m": m, "n": n, "fp64_ms": time_gram(lib, P, G, scratch, ex, nb, m_pad, batch, 0)}
-    for order in (0, 1, 2):
-        os.environ["ASVD_GI_ORDER"] = str(order)
-        t = time_gram(lib, P, G, scratch, ex, nb, m_pad, batch, 1)
-        out[f"i8_order{order}_ms_incl_colmax_split"] = t
-        out[f"i8_order{order}_Pops_if_all_gemm"] = ops_per / t / 1e12
-    os.environ.pop("ASVD_GI_ORDER")
+    t = time_gram(lib, P, G, scratch, ex, nb, m_pad, batch, 1)
+    out["i8_ms_incl_colmax_split"] = t
+    out["i8_Pops_if_all_gemm"] = ops_per / t / 1e12
     print(json.dumps(out), flush=True)
     del P, G, scratch
     torch.cuda.empty_cache()
@@ -51,8 +48,7 @@ def main():
     mats = [torch.randn(m, n, device=dev, generator=g) * 0.02 for _ in range(batch)]
     scales = [1 + 30 * torch.rand(n, device=dev, generator=g) ** 8 for _ in range(batch)]
     os.environ["ASVD_SPLIT"] = "0"
-    for name, env in (("bf16_long_side", {"ASVD_NN_I8": "0"}), ("i8_order1", {"ASVD_NI_ORDER": "1"}), ("i8_order0", {"ASVD_NI_ORDER": "0"}),
-                      ("i8_order2", {"ASVD_NI_ORDER": "2"}), ("gram_fp64", {"ASVD_GRAM_I8": "0"}), ("gram_i8_order1", {"ASVD_GI_ORDER": "1"})):
+    for name, env in (("bf16_long_side", {"ASVD_NN_I8": "0"}), ("i8", {}), ("gram_fp64", {"ASVD_GRAM_I8": "0"})):
         for k, v in env.items():
             os.environ[k] = v
         ops.svd_batched(mats, scales)
