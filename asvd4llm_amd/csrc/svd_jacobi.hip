@@ -22,6 +22,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstdarg>
 #include <algorithm>
 #include <type_traits>
 #include <thread>
@@ -65,7 +66,7 @@ struct Plan {
     int64_t m, n;         // as given
     int transposed;       // oriented = A^T when m < n
     int rows, cols;       // oriented dims, rows >= cols
-    int m_pad, n_pad, nb, npairs, R, R_upd, want_v, vmode;  // vmode: 0 no right vectors, 2 backsolve at the end (1, accumulate V in the sweeps, is gone)
+    int m_pad, n_pad, nb, npairs, R, vmode;  // vmode: 0 no right vectors, 2 backsolve at the end (1, accumulate V in the sweeps, is gone)
     int nsplit, rows_per_split, rows_per_wg, nchunks;
     // two-level dense sweeps (twolevel.h): ns super-panels of 64 columns, npairs_s pair slots per super-step (power-of-two padded)
     int two, ns, npairs_s, nsplit_s, rows_per_split_s, nchunks_s, rows_per_wg_s, nchunks_q, rows_per_wg_q;
@@ -75,8 +76,10 @@ struct Plan {
     size_t off_x, off_xorig, off_gpart, off_q, off_active, off_sig, off_ina, off_inv, off_perm, off_flags, off_pflag, off_plist, off_snap, off_snapex, total;
 };
 
-int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p) {
-    if (batch < 1 || m < 1 || n < 1 || m > (1 << 24) || n > (1 << 24)) return ASVD_E_BADARG;
+constexpr int64_t MAX_DIM = 1 << 24;   // largest m and n of a call
+
+int make_plan(int batch, int64_t m, int64_t n, int want_vv, Plan& p) {
+    if (batch < 1 || m < 1 || n < 1 || m > MAX_DIM || n > MAX_DIM) return ASVD_E_BADARG;
     // CUs the launches of the current call may use: those of the device (256 on the MI355X), or those of one half when asvd_svd_batched runs a
     // batch as two halves on CU-masked streams (below).  The launch geometry of a plan (row splits, chunk counts) is sized for this many.
     const int64_t cu = call_cus_now();
@@ -94,11 +97,9 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
         while (pw2 < p.nb) pw2 <<= 1;
         p.npairs = pw2 / 2;  // XOR ordering runs over the panel count padded to a power of two
     }
-    // want_u / want_vv: left / right vectors OF THE ORIENTED problem (columns of the rotated matrix / backsolved V rows)
-    p.want_v = (want_u || want_vv) ? 1 : 0;
+    // want_vv: right vectors OF THE ORIENTED problem (backsolved V rows)
     p.vmode = want_vv ? 2 : 0;
-    p.R = p.m_pad + (want_vv ? p.n_pad : 0);   // the V rows of a panel are written by the backsolve at the end, never rotated
-    p.R_upd = p.m_pad;
+    p.R = p.m_pad + (want_vv ? p.n_pad : 0);   // the V rows of a panel are written by the backsolve at the end, never rotated: updates cover m_pad rows
     // gram: choose the row split that minimises (rounds of resident workgroups) x (chunks per wave + fixed overhead).
     // 3 workgroups of 4 waves fit per CU (148 VGPR+AGPR) -> 768 slots; a grid of 1.3 x slots costs 2 full rounds.
     {
@@ -118,10 +119,10 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
     }
     // update: 128-row iterations; aim for >= 1024 workgroups but >= 2 iterations per workgroup when possible
     int64_t wantc = ceil_div64(4 * cu, (int64_t)p.npairs * batch);
-    int64_t iters_total = ceil_div64(p.R_upd, 128);
+    int64_t iters_total = ceil_div64(p.m_pad, 128);
     int64_t nc = wantc < 1 ? 1 : (wantc > iters_total ? iters_total : wantc);
     p.rows_per_wg = (int)(ceil_div64(iters_total, nc) * 128);
-    p.nchunks = (int)ceil_div64(p.R_upd, p.rows_per_wg);
+    p.nchunks = (int)ceil_div64(p.m_pad, p.rows_per_wg);
     {
         // two-level dense sweeps for >= 8 panels; smaller problems run the single-level sweep
         p.two = p.nb >= 8 ? 1 : 0;
@@ -143,11 +144,11 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
         p.rows_per_split_s = (int)(ceil_div64(nchunk_total, best_ns) * 32);
         p.nsplit_s = (int)ceil_div64(p.m_pad, p.rows_per_split_s);
         // supdate: 32-row tiles; aim for >= 1024 workgroups per launch and >= 4 tiles per workgroup
-        const int64_t tiles = ceil_div64(p.R_upd, 32);
+        const int64_t tiles = ceil_div64(p.m_pad, 32);
         int64_t wantc = ceil_div64(4 * cu, (int64_t)p.npairs_s * batch);
         int64_t nc = std::max<int64_t>(1, std::min<int64_t>(wantc, ceil_div64(tiles, 4)));
         p.rows_per_wg_s = (int)(ceil_div64(tiles, nc) * 32);
-        p.nchunks_s = (int)ceil_div64(p.R_upd, p.rows_per_wg_s);
+        p.nchunks_s = (int)ceil_div64(p.m_pad, p.rows_per_wg_s);
         // supgram (update of a step fused with the Gram tiles of the next): one 512-thread workgroup per CU and quad of four
         // super-panels; ~512 workgroups per launch where the rows allow >= 8 tiles each
         // measured (16 x 4096^2): 2 chunks (512 workgroups) beat 4 and 8 — longer streams per workgroup, fewer partial tiles for the solves to sum
@@ -170,7 +171,7 @@ int make_plan(int batch, int64_t m, int64_t n, int want_u, int want_vv, Plan& p)
             }
         }
         p.rows_per_wg_q = (int)(ceil_div64(tiles, nq) * 32);
-        p.nchunks_q = (int)ceil_div64(p.R_upd, p.rows_per_wg_q);
+        p.nchunks_q = (int)ceil_div64(p.m_pad, p.rows_per_wg_q);
     }
     p.panel_stride = (int64_t)p.R * PB;
     p.batch_stride = p.panel_stride * p.nb;
@@ -253,65 +254,112 @@ static bool super_grouped_for(const Plan& p) {
     return p.two && grouped_applies(p.ns);
 }
 
+// test hook asvd_test_super_schedule: slot k of super-step `step` of the super-panel pair schedule
+__global__ void super_schedule_kernel(Sched sc, int ns, int nsteps, int npairs, int* __restrict__ out) {
+    const int step = blockIdx.x, k = threadIdx.x;
+    if (k >= npairs) return;
+    int S, T;
+    super_pair(sc, ns, step, k, S, T);
+    out[step * npairs + k] = (S < ns && T < ns) ? ((S << 16) | T) : -1;
+}
+
+// what svd_tall and the split of a batch return when they do not apply: the caller then runs the plain call
+constexpr int NOT_APPLICABLE = -100;   // the reduction (Cholesky breakdown, workspace too small for it), or the split (workspace, sizes)
+constexpr int SPLIT_REFUSED = -101;    // the split: refused (another process on the device, a CU-masked caller stream, no CU-masked streams)
+
+// ASVD_DEBUG: one line of the driver's trace on stderr
+__attribute__((format(printf, 1, 2))) static void debug_trace(const char* fmt, ...) {
+    if (!getenv("ASVD_DEBUG")) return;
+    char line[512];
+    va_list ap;
+    va_start(ap, fmt); vsnprintf(line, sizeof(line), fmt, ap); va_end(ap);
+    fprintf(stderr, "[asvd_svd] %s\n", line);
+}
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // ---- optional per-class timing with HIP events on the call's stream ------------------------------
-// profiling state is per host thread: concurrent calls from different threads (on their own streams and workspaces) do not share it
-thread_local bool g_prof_enabled = false;
-thread_local int g_prof_mode = 0;   // asvd_svd_set_profiling: 0 off, 1 profile (the call runs UNSPLIT: every kernel alone on the chip), 2 profile and keep the split
 // classes: 0 pack / reduce, 1 two-level Gram pass, 2 eigen-solves, 3 two-level update pass, 4 finalize, 5 coupling snapshot,
-//          6 single-level Gram, 7 single-level update
+//          6 single-level Gram, 7 single-level update, 8 fused two-level update + Gram pass
 constexpr int NPROF = 9;
-thread_local float g_prof_ms[NPROF] = {0};
-thread_local int g_prof_launches[NPROF] = {0};
-thread_local long long g_prof_pairs[3] = {0, 0, 0};  // 32-panel pair visits, rotated 32-panel pairs, updated super-pairs (two-level sweeps)
-thread_local std::vector<float> g_prof_sweep_ms;       // wall time of every sweep of the last profiled call (all problems of the batch together)
-thread_local std::vector<long long> g_prof_sweep_rot;  // pairs rotated in it  // {pair visits (gram), rotated pairs (evd + update)} of the last profiled call
 struct ProfRec { int cls; hipEvent_t a, b; };
-thread_local std::vector<ProfRec> g_prof_recs;
-// split-mode profile (mode 2): both halves time their own launches with events on their own stream; `g_prof_base` is an event recorded on the
-// caller's stream before the halves start, so that the [start, end] of every fused update + Gram launch (class 8) of both halves can be placed
-// on ONE time axis — the union / overlap of the two halves' HBM-bound launches is what the combined streaming rate of a split step follows from
-thread_local hipEvent_t g_prof_base = nullptr;
-thread_local std::vector<std::pair<float, float>> g_prof_iv8;
-thread_local bool g_prof_last_split = false;
-thread_local float g_prof_half_ms[2][9] = {{0}};
-thread_local int g_prof_half_launches[2][9] = {{0}};
-thread_local float g_prof_overlap[4] = {0, 0, 0, 0};   // class 8: summed ms of half 0, of half 1, union of both, time BOTH were in it
+// What the profiled calls of ONE host thread measured: concurrent calls from different threads (on their own streams and workspaces) do not
+// share it.  The second half of a split call fills the record of the worker thread, which hands the whole record back to the caller.
+struct Profile {
+    bool on = false;                           // asvd_svd_set_profiling
+    float ms[NPROF] = {};
+    int launches[NPROF] = {};
+    long long pairs[3] = {};                   // 32-panel pair visits, rotated 32-panel pairs, updated super-pairs (two-level sweeps)
+    std::vector<float> sweep_ms;               // wall time of every sweep of the last profiled call (all problems of the batch together)
+    std::vector<long long> sweep_rot;          // pairs rotated in it
+    std::vector<ProfRec> recs;                 // event pairs not yet read
+    std::vector<std::pair<float, float>> iv8;  // [start, end] of every class-8 launch, ms after the base event given to end()
+    void begin() { *this = Profile{on}; }
+    // base: an event recorded before the call started (split mode, below), or nullptr: no class-8 intervals
+    void end(hipEvent_t base) {
+        for (auto& r : recs) {
+            float t = 0;
+            (void)hipEventSynchronize(r.b);
+            (void)hipEventElapsedTime(&t, r.a, r.b);
+            ms[r.cls] += t;
+            launches[r.cls] += 1;
+            if (r.cls == 8 && base) {
+                float t0 = 0;
+                if (hipEventElapsedTime(&t0, base, r.a) == hipSuccess) iv8.emplace_back(t0, t0 + t);
+            }
+            (void)hipEventDestroy(r.a);
+            (void)hipEventDestroy(r.b);
+        }
+        recs.clear();
+    }
+    void add(const Profile& o) {
+        for (int i = 0; i < NPROF; ++i) { ms[i] += o.ms[i]; launches[i] += o.launches[i]; }
+        for (int i = 0; i < 3; ++i) pairs[i] += o.pairs[i];
+    }
+};
+thread_local Profile g_prof;
+thread_local bool g_prof_keep_split = false;   // asvd_svd_set_profiling(2): a profiled call keeps the split (else it runs UNSPLIT: every kernel alone on the chip)
+// The split-mode profile (mode 2): both halves time their own launches with events on their own stream, and the [start, end] of every fused
+// update + Gram launch (class 8) of both halves is placed on ONE time axis — the union / overlap of the two halves' HBM-bound launches is what
+// the combined streaming rate of a split step follows from.
+struct SplitProfile {
+    bool last = false;   // the last asvd_svd_batched call of this thread ran split
+    float ms[2][NPROF] = {};
+    int launches[2][NPROF] = {};
+    float overlap[4] = {};   // class 8: summed ms of half 0, of half 1, union of both, time BOTH were in it
+};
+thread_local SplitProfile g_split_prof;
 // which path the last asvd_svd_batched call of this host thread took (asvd_svd_get_last_path): ASVD_PATH_* bits of include/asvd_hip.h
 thread_local int g_last_path = 0;
 
+// class-8 intervals of both halves on one time axis -> SplitProfile::overlap
+static void class8_overlap(const std::vector<std::pair<float, float>>& iv0, const std::vector<std::pair<float, float>>& iv1, float out[4]) {
+    std::vector<std::pair<float, int>> edges;
+    float sum[2] = {0, 0};
+    for (int h = 0; h < 2; ++h)
+        for (auto& iv : h ? iv1 : iv0) { edges.emplace_back(iv.first, +1); edges.emplace_back(iv.second, -1); sum[h] += iv.second - iv.first; }
+    std::sort(edges.begin(), edges.end());
+    float uni = 0, both = 0, last = 0;
+    int depth = 0;
+    for (auto& e : edges) {
+        if (depth >= 1) uni += e.first - last;
+        if (depth >= 2) both += e.first - last;
+        last = e.first;
+        depth += e.second;
+    }
+    out[0] = sum[0]; out[1] = sum[1]; out[2] = uni; out[3] = both;
+}
+
 struct ProfScope {
     int cls; hipStream_t st; hipEvent_t a = nullptr, b = nullptr; bool on;
-    ProfScope(int c, hipStream_t s) : cls(c), st(s), on(g_prof_enabled) {
+    ProfScope(int c, hipStream_t s) : cls(c), st(s), on(g_prof.on) {
         if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, st); }
     }
     ~ProfScope() {
-        if (on) { (void)hipEventRecord(b, st); g_prof_recs.push_back({cls, a, b}); }
+        if (on) { (void)hipEventRecord(b, st); g_prof.recs.push_back({cls, a, b}); }
     }
 };
-void prof_begin() {
-    for (int i = 0; i < NPROF; ++i) { g_prof_ms[i] = 0; g_prof_launches[i] = 0; }
-    g_prof_pairs[0] = g_prof_pairs[1] = g_prof_pairs[2] = 0;
-    g_prof_sweep_ms.clear();
-    g_prof_sweep_rot.clear();
-    g_prof_recs.clear();
-    g_prof_iv8.clear();
-}
-void prof_end() {
-    for (auto& r : g_prof_recs) {
-        float ms = 0;
-        (void)hipEventSynchronize(r.b);
-        (void)hipEventElapsedTime(&ms, r.a, r.b);
-        g_prof_ms[r.cls] += ms;
-        g_prof_launches[r.cls] += 1;
-        if (r.cls == 8 && g_prof_base) {
-            float t0 = 0;
-            if (hipEventElapsedTime(&t0, g_prof_base, r.a) == hipSuccess) g_prof_iv8.emplace_back(t0, t0 + ms);
-        }
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    g_prof_recs.clear();
-}
 
 template <int DT>
 int launch_pack(const void* src, int64_t ld, const void* s, int cs_dtype, const Plan& p, float* Xb, hipStream_t st) {
@@ -342,62 +390,763 @@ int pack_batch(const void* const* a_host, int a_dtype, int64_t lda, const void* 
     return ASVD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void asvd_svd_set_profiling(int enabled) { g_prof_enabled = enabled != 0; g_prof_mode = enabled < 0 ? 0 : (enabled > 2 ? 1 : enabled); }
-int asvd_svd_get_split_profile(float* ms_host, int* launches_host, float* overlap_host) {
-    if (!ms_host || !launches_host || !overlap_host) return ASVD_E_BADARG;
-    for (int h = 0; h < 2; ++h)
-        for (int i = 0; i < NPROF; ++i) { ms_host[h * NPROF + i] = g_prof_half_ms[h][i]; launches_host[h * NPROF + i] = g_prof_half_launches[h][i]; }
-    for (int i = 0; i < 4; ++i) overlap_host[i] = g_prof_overlap[i];
-    return g_prof_last_split ? 1 : 0;
-}
-// CUs the calls of THIS host thread may use (0 = the whole device): a caller that runs asvd_svd_batched on a CU-masked stream of its own says so
-// here, so that the launch geometry (row splits, chunk counts, launch forms) is sized for those CUs; such calls are never split again.
-void asvd_svd_set_call_cus(int cus) { g_call_cus = cus > 0 ? cus : 0; }
-int asvd_svd_get_sweep_times(float* ms_host, long long* rotated_host, int cap) {
-    const int n = (int)g_prof_sweep_ms.size();
-    for (int i = 0; i < n && i < cap; ++i) {
-        if (ms_host) ms_host[i] = g_prof_sweep_ms[i];
-        if (rotated_host) rotated_host[i] = g_prof_sweep_rot[i];
+// Sparse sweeps: marks -> lists of disjoint pairs.  The pairs of one XOR step (I ^ J == d) are disjoint by construction, but late in the
+// iteration a step holds a handful of pairs and a sweep of nb-1 three-launch steps is all launch latency.  The marked pairs of every running
+// problem (flags: [batch][nb][nb], host_done: [batch]) are therefore packed first-fit, in schedule order (step, then I), into at most nsteps
+// ROUNDS whose pairs share no panel (per problem: a bitmask of used panels per round); a round is launched like a step.  Any order of disjoint
+// rotations is a valid Jacobi sweep; first-fit keeps the nearest-neighbour-first order of the XOR schedule among conflicting pairs.
+// list: cnt[r] slots per problem for round r from off[r] on (code I << 16 | J, -1 = empty slot).  Returns the number of marked pairs.
+static long long pack_marked_pairs(const std::vector<unsigned char>& flags, const std::vector<int>& host_done, int nb, int nsteps,
+                                   std::vector<int>& list, std::vector<int>& off, std::vector<int>& cnt) {
+    const int batch = (int)host_done.size();
+    long long marked_total = 0;
+    list.clear();
+    std::vector<std::vector<int>> tmp((size_t)batch * nsteps);  // [b * nsteps + round]
+    const int words = (nb + 63) / 64;
+    std::vector<uint64_t> used;  // [round][words] of the problem being packed
+    for (int b = 0; b < batch; ++b) {
+        if (host_done[b]) continue;
+        const unsigned char* f = flags.data() + (size_t)b * nb * nb;
+        bool packed = true;
+        used.assign((size_t)nsteps * words, 0);
+        long long n = 0;
+        for (int d = 1; d <= nsteps && packed; ++d)
+            for (int I = 0; I < nb && packed; ++I) {
+                const int J = I ^ d;
+                if (J <= I || J >= nb || !f[(size_t)I * nb + J]) continue;
+                int r = 0;
+                for (; r < nsteps; ++r) {
+                    uint64_t* u = &used[(size_t)r * words];
+                    if (!((u[I >> 6] >> (I & 63)) & 1) && !((u[J >> 6] >> (J & 63)) & 1)) {
+                        u[I >> 6] |= 1ull << (I & 63);
+                        u[J >> 6] |= 1ull << (J & 63);
+                        break;
+                    }
+                }
+                if (r == nsteps) { packed = false; break; }  // cannot happen below ~nsteps/2 marks per panel; fall back
+                tmp[(size_t)b * nsteps + r].push_back((I << 16) | J);
+                ++n;
+            }
+        if (packed) marked_total += n;
+        else {  // one list per XOR step
+            for (int r = 0; r < nsteps; ++r) tmp[(size_t)b * nsteps + r].clear();
+            for (int I = 0; I < nb; ++I)
+                for (int J = I + 1; J < nb; ++J)
+                    if (f[(size_t)I * nb + J]) { tmp[(size_t)b * nsteps + ((I ^ J) - 1)].push_back((I << 16) | J); ++marked_total; }
+        }
     }
-    return n;
+    for (int r = 0; r < nsteps; ++r) {
+        size_t mx = 0;
+        for (int b = 0; b < batch; ++b) mx = std::max(mx, tmp[(size_t)b * nsteps + r].size());
+        cnt[r] = (int)mx;
+        off[r] = (int)list.size();
+        for (int b = 0; b < batch; ++b) {
+            const auto& v = tmp[(size_t)b * nsteps + r];
+            for (size_t i = 0; i < mx; ++i) list.push_back(i < v.size() ? v[i] : -1);
+        }
+    }
+    return marked_total;
 }
 
-int asvd_svd_get_last_path(void) { return g_last_path; }
-
-int asvd_svd_get_pair_counts(long long* counts_host) {
-    if (!counts_host) return ASVD_E_BADARG;
-    counts_host[0] = g_prof_pairs[0];
-    counts_host[1] = g_prof_pairs[1];
-    counts_host[2] = g_prof_pairs[2];
-    return ASVD_OK;
-}
-
-int asvd_svd_get_profile(float* ms_host, int* launches_host) {
-    if (!ms_host || !launches_host) return ASVD_E_BADARG;
-    for (int i = 0; i < NPROF; ++i) { ms_host[i] = g_prof_ms[i]; launches_host[i] = g_prof_launches[i]; }
-    return ASVD_OK;
-}
-
-// forward declarations of the tall-path helpers (defined after the direct driver)
-static bool tall_wanted(const Plan& p);
-static size_t tall_worksize(int batch, int64_t m, int64_t n, int want_vectors, int64_t k);
-
-// workspace of ONE call of `batch` problems whose launches are sized for the CUs of the current thread (call_cus_now())
-static int worksize_one(int batch, int64_t m, int64_t n, int want_vectors, size_t* bytes) {
+// ---- the direct driver: sweeps on the packed panels, then finalize ----------------------------------------------------------------------
+// The fixed state of one call: its plan, the workspace as the kernels see it, the schedule and the stream.
+struct Direct {
     Plan p;
-    int rc = make_plan(batch, m, n, want_vectors, want_vectors, p);
-    if (rc) return rc;
-    size_t need = p.total;  // the direct path is always available as the fallback
-    if (tall_wanted(p)) {
-        const size_t t = tall_worksize(batch, m, n, want_vectors, p.cols);
-        if (t > need) need = t;
+    hipStream_t st;
+    char* wb;
+    float *X, *Gpart, *Qbuf, *sig, *ina, *inv;
+    int *active, *perm, *nrot, *done, *nupd, *plist;
+    unsigned* maxoff;
+    unsigned char* pflag;   // sparse-sweep pair marks (see fullcheck_kernel)
+    Sched sc;               // the call's schedule description: a kernel argument of every launch (no process-global device state)
+    EvdV3 v3;               // buffers of the two-level sweeps as the kernels see them
+    int kb;                 // panels whose convergence is enforced: those holding the k leading columns, plus one panel of margin
+    int nsteps;             // steps of a single-level sweep (XOR distances 1 .. nsteps)
+    float tol;
+};
+// one inner sweep of the 64x64 eigen-solve per visit: with the XOR schedule a second one no longer saves outer sweeps
+// (measured 26.3 vs 25.9 SVD/s)
+constexpr int inner_sweeps = 1;
+
+static void direct_bind(Direct& c, void* work, hipStream_t st, int64_t k, float tol) {
+    const Plan& p = c.p;
+    char* wb = (char*)work;
+    c.st = st;
+    c.wb = wb;
+    c.X = (float*)(wb + p.off_x); c.Gpart = (float*)(wb + p.off_gpart); c.Qbuf = (float*)(wb + p.off_q); c.active = (int*)(wb + p.off_active);
+    c.sig = (float*)(wb + p.off_sig); c.ina = (float*)(wb + p.off_ina); c.inv = (float*)(wb + p.off_inv); c.perm = (int*)(wb + p.off_perm);
+    // flags: [maxoff bits | nrot | done | super-pair updates (instrumentation)] x batch (SoA)
+    c.maxoff = (unsigned*)(wb + p.off_flags);
+    c.nrot = (int*)(wb + p.off_flags) + p.batch;
+    c.done = (int*)(wb + p.off_flags) + 2 * p.batch;
+    c.nupd = (int*)(wb + p.off_flags) + 3 * p.batch;
+    c.pflag = (unsigned char*)(wb + p.off_pflag);
+    c.plist = (int*)(wb + p.off_plist);
+    c.sc = default_sched();
+    c.sc.super_order = super_grouped_for(p) ? 2 : 1;
+    if (c.sc.super_order == 2) set_group_table(c.sc, p.ns, group_bits_for(p.ns));
+    c.v3 = EvdV3{};
+    c.v3.ns = p.ns;
+    c.v3.nbpan = p.nb;
+    c.v3.Gd32 = (float*)(wb + p.off_gd32); c.v3.Q0 = (float*)(wb + p.off_q0); c.v3.D0 = (float*)(wb + p.off_d0);
+    c.v3.Qfin = (float*)(wb + p.off_qfin); c.v3.subact = (int*)(wb + p.off_subact); c.v3.Din = (float*)(wb + p.off_din);
+    c.kb = (int)(ceil_div64(k, PB) + 1 < p.nb ? ceil_div64(k, PB) + 1 : p.nb);
+    c.nsteps = 2 * p.npairs - 1;
+    c.tol = tol;
+}
+
+static int direct_pack(const Direct& c, const void* const* a_host, int a_dtype, int64_t lda, const void* const* cs_host, int cs_dtype) {
+    const Plan& p = c.p;
+    ProfScope ps(0, c.st);
+    ASVD_HIP_CHECK(hipMemsetAsync(c.X, 0, (size_t)p.batch_stride * p.batch * sizeof(float), c.st));
+    ASVD_HIP_CHECK(hipMemsetAsync(c.wb + p.off_flags, 0, (size_t)p.batch * 4 * sizeof(int), c.st));
+    if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, c.X, c.st)) return prc;
+    if (p.vmode == 2) {
+        // keep the packed original (A rows of every panel) for the final backsolve
+        ASVD_HIP_CHECK(hipMemcpy2DAsync(c.wb + p.off_xorig, (size_t)p.m_pad * PB * sizeof(float), c.X, (size_t)p.R * PB * sizeof(float),
+                                        (size_t)p.m_pad * PB * sizeof(float), (size_t)p.nb * p.batch, hipMemcpyDeviceToDevice, c.st));
     }
-    *bytes = need;
     return ASVD_OK;
+}
+
+// Step schedule of a single-level dense sweep (XOR distances d, stored as step = d-1).  The local levels d = 1..L are run twice at the
+// start of every sweep: the strongest couplings of the sorted, preconditioned matrix sit between neighbouring panels, and a second pass
+// over them is cheap (L extra steps of P-1) — docs/history.md (round 1).  L = min(7, P/16 - 1): measured at 4096^2 (P = 128) 8 -> 7 sweeps, +2.4 %.
+static std::vector<int> single_level_schedule(int nsteps) {
+    std::vector<int> sched;
+    const int P2 = nsteps + 1;
+    const int L = std::min(std::max(0, std::min(7, P2 / 16 - 1)), nsteps);
+    for (int d = 1; d <= L; ++d) sched.push_back(d - 1);
+    for (int st2 = 0; st2 < nsteps; ++st2) sched.push_back(st2);
+    return sched;
+}
+
+// marks of the coupling snapshot (host copy) and the rounds of disjoint pairs packed from them (pack_marked_pairs)
+struct SparseLists { std::vector<unsigned char> marks; std::vector<int> list, off, cnt; };
+
+// Opens a sparse sweep: snapshot of all couplings, marks read back, packed into rounds of disjoint pairs, the lists uploaded.
+static int sparse_snapshot(const Direct& c, const std::vector<int>& host_done, SparseLists& sl, long long* marked,
+                           std::chrono::steady_clock::time_point t0) {
+    const Plan& p = c.p; const int batch = p.batch; const hipStream_t st = c.st;
+    float* dnorm = c.ina;  // squared column norms of the snapshot (finalize overwrites this buffer later)
+    {
+        ProfScope ps(5, st);
+        ASVD_HIP_CHECK(hipMemsetAsync(c.pflag, 0, (size_t)batch * p.nb * p.nb, st));
+        const unsigned nt = (unsigned)ceil_div64(p.nb, 4);
+        const char* es8 = getenv("ASVD_SNAP_I8");   // read per call
+        const bool snap8 = p.nb >= 8 && p.m_pad <= 32768 && !(es8 && atoi(es8) == 0);
+        if (snap8) panel_sumsq_max_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(c.X, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, dnorm, (int*)(c.wb + p.off_snapex), c.done);
+        else panel_sumsq_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, dnorm, c.done);
+        if (snap8) {
+            // X^T X from int8 digit planes (snapshot_i8.h): digitise once, eight exact digit products per fp32 product
+            int* sex = (int*)(c.wb + p.off_snapex);
+            signed char* spl = (signed char*)(c.wb + p.off_snap);
+            const int kgs = (int)(round_up64(p.m_pad, 64) / 16);
+            const int64_t plane_stride = (int64_t)p.nb * kgs * 512;
+            split_i8_kernel<<<dim3(p.nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(c.X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, sex, 0,
+                                                                                           kgs, spl, plane_stride, nullptr, c.done);
+            ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)fullcheck_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
+            fullcheck_i8_kernel<<<dim3(nt * (nt + 1) / 2, batch), 512, 2 * GI_STAGE_BYTES, st>>>(spl, plane_stride, p.nb, kgs, p.n_pad, sex, dnorm, c.tol, c.kb,
+                                                                                              c.pflag, c.maxoff, c.done, (int)nt);
+        } else {
+            fullcheck_kernel<<<dim3(nt, nt, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, dnorm, c.tol, c.kb, c.pflag,
+                                                                  c.maxoff, c.done);
+        }
+    }
+    sl.marks.resize((size_t)batch * p.nb * p.nb);
+    ASVD_HIP_CHECK(hipMemcpyAsync(sl.marks.data(), c.pflag, sl.marks.size(), hipMemcpyDeviceToHost, st));
+    ASVD_HIP_CHECK(hipStreamSynchronize(st));
+    debug_trace("  snapshot + readback %.2f ms", ms_since(t0));
+    sl.off.resize(c.nsteps);
+    sl.cnt.resize(c.nsteps);
+    *marked = pack_marked_pairs(sl.marks, host_done, p.nb, c.nsteps, sl.list, sl.off, sl.cnt);
+    debug_trace("  lists built at %.2f ms (%zu slots)", ms_since(t0), sl.list.size());
+    if (!sl.list.empty()) ASVD_HIP_CHECK(hipMemcpyAsync(c.plist, sl.list.data(), sl.list.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    return ASVD_OK;
+}
+
+// The rounds of a sparse sweep, three single-level launches each.
+static void sparse_rounds(const Direct& c, const SparseLists& sl) {
+    const Plan& p = c.p; const int batch = p.batch; const hipStream_t st = c.st;
+    for (int step = 0; step < c.nsteps; ++step) {
+        const int slots = sl.cnt[step];
+        if (slots == 0) continue;  // no marked pair meets in this round
+        const int* pl = c.plist + sl.off[step];
+        // few pairs per launch: split the rows further to fill the CUs, within the partial-Gram capacity of a problem
+        const int64_t chunks = p.m_pad / 32, cap = (int64_t)p.npairs * p.nsplit / slots;
+        int64_t ns = std::max<int64_t>(p.nsplit, ceil_div64(3 * call_cus_now(), (int64_t)slots * batch));
+        ns = std::min<int64_t>(std::min<int64_t>(ns, cap), std::min<int64_t>(chunks, 64));
+        if (ns < 1) ns = 1;
+        const int rps = (int)(ceil_div64(chunks, ns) * 32);
+        const int nsp = (int)ceil_div64(p.m_pad, rps);
+        const int64_t iters = ceil_div64(p.m_pad, 128);
+        int64_t nc = std::min<int64_t>(iters, std::max<int64_t>(1, ceil_div64(4 * call_cus_now(), (int64_t)slots * batch)));
+        const int rpw = (int)(ceil_div64(iters, nc) * 128);
+        const int nch = (int)ceil_div64(p.m_pad, rpw);
+        {
+            ProfScope ps(6, st);
+            gram_kernel<<<dim3(nsp, slots, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, rps, c.Gpart, c.done, pl, slots);
+        }
+        {
+            ProfScope ps(2, st);
+            launch_evdw0(false, slots, batch, st, c.sc, c.Gpart, nsp, c.Qbuf, c.active, c.maxoff, c.nrot, c.done, c.tol, inner_sweeps, p.nb, step, c.kb, pl, slots, EvdV3{});
+        }
+        {
+            ProfScope ps(7, st);
+            update_kernel<<<dim3(nch, slots, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, rpw, c.Qbuf, c.active, c.done, pl, slots);
+        }
+    }
+}
+
+// Dense single-level steps, three launches each.  carry: the internal step of a two-level sweep, whose eigen-solves also emit the fresh
+// carried diagonal blocks of both panels of every pair.
+static void single_level_steps(const Direct& c, const std::vector<int>& steps, bool carry) {
+    const Plan& p = c.p; const int batch = p.batch; const hipStream_t st = c.st;
+    for (const int step : steps) {
+        {
+            ProfScope ps(6, st);
+            gram_kernel<<<dim3(p.nsplit, p.npairs, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, p.rows_per_split, c.Gpart,
+                                                                      c.done, nullptr, 0);
+        }
+        {
+            ProfScope ps(2, st);
+            launch_evdw0(carry, p.npairs, batch, st, c.sc, c.Gpart, p.nsplit, c.Qbuf, c.active, c.maxoff, c.nrot, c.done, c.tol, inner_sweeps, p.nb, step, c.kb,
+                         nullptr, 0, carry ? c.v3 : EvdV3{});
+        }
+        {
+            ProfScope ps(7, st);
+            update_kernel<<<dim3(p.nchunks, p.npairs, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, p.rows_per_wg, c.Qbuf,
+                                                                         c.active, c.done, nullptr, 0);
+        }
+    }
+}
+
+// The super-steps of a two-level dense sweep, two or three launches each.  *fused_used: the fused update + Gram kernel ran.
+static int super_steps(Direct& c, bool allow_f16, bool* fused_used) {
+    const Plan& p = c.p; const int batch = p.batch; const hipStream_t st = c.st;
+    float* Gx6 = (float*)(c.wb + p.off_gx6);
+    const bool super_grp = super_grouped_for(p);
+    const int sgb = super_grp ? group_bits_for(p.ns) : 0, sG1 = (1 << sgb) - 1;   // grouped schedule: group size - 1
+    const int nsuper = super_grp ? grouped_steps(p.ns, sgb) : 2 * p.npairs_s - 1;
+    // supgram: the update of step D also leaves the Gram tiles of the step that follows (one pass instead of two); the stand-alone Gram
+    // pass then runs only in front of the first super-step.  ASVD_SUPGRAM=0 keeps the separate passes (fp32 Gram pass, split-bf16 update
+    // pass: also what a call falls back to when the split-fp16 path of the fused kernel turns a problem NaN).
+    const bool fuse_ug = allow_f16 && p.npairs_s >= 2 && !(getenv("ASVD_SUPGRAM") && atoi(getenv("ASVD_SUPGRAM")) == 0);
+    *fused_used = *fused_used || fuse_ug;
+    if (fuse_ug)
+        ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)supgram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SUPGRAM_SMEM_FLOATS * sizeof(float))));
+    // on a padded XOR schedule (ns not a power of two and no grouped schedule) many super-steps hold few real pairs and the fused kernel,
+    // which reads every panel of a quad with a present member, loses to the separate passes, which touch only the pairs that exist
+    // (13B shapes, ns = 80 in a 128-wide schedule: always fused 21.4 s, never fused 16.9 s for the model): fused on full schedules only
+    const bool ns_pow2 = (p.ns & (p.ns - 1)) == 0;
+    // (Round 5 measured a LINE-SPREAD order of the distances from a given dense sweep on — triples {d, w(d), w^2(d)} that close the four
+    // super-panels of a quad — against this one: slower from every starting sweep, profiles/r5_spread_order_from_sweep.txt; removed.)
+    auto fused_after = [&](int dj) {  // does the launch of super-step index dj also leave the tiles of index dj + 1 ?
+        if (!fuse_ug || dj < 0 || dj + 1 >= nsuper) return false;
+        if (super_grp) {  // consecutive steps inside the groups (XOR distances 1..15), or consecutive offsets of the same round of group pairs
+            const int s0 = dj, s1 = dj + 1;   // 0-based super-steps
+            return s1 < sG1 || (s0 >= sG1 && ((s0 - sG1) >> sgb) == ((s1 - sG1) >> sgb));
+        }
+        return ns_pow2;
+    };
+    EvdV3& v3 = c.v3;
+    for (int di = 0; di < nsuper; ++di) {
+        const int D = di + 1;
+        const int E = (di + 1 < nsuper) ? di + 2 : 0;  // 0: last super-step of the sweep
+        const bool gram_in = !fused_after(di - 1);   // tiles of this step not left by the previous launch
+        const bool gram_out = fused_after(di);
+        v3.nsplit6 = gram_in ? p.nsplit_s : p.nchunks_q;
+        v3.Gx6 = Gx6;
+        if (gram_in) {
+            ProfScope ps(1, st);
+            sgram6_kernel<<<dim3(p.nsplit_s, p.npairs_s, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.ns, D, p.m_pad, p.rows_per_split_s, Gx6, c.done);
+        }
+        {
+            ProfScope ps(2, st);  // both inner steps of every super-pair in one launch, one wave per 64x64 solve (evd_wave.hip)
+            launch_evdw12(p.npairs_s, batch, st, c.sc, c.maxoff, c.nrot, c.done, c.tol, inner_sweeps, p.nb, D - 1, c.kb, v3, p.cols >= 2048);
+        }
+        {
+            ProfScope ps(gram_out ? 8 : 3, st);
+            if (gram_out)
+                supgram_kernel<<<dim3(p.nchunks_q, (2 * p.npairs_s) / 4, batch), 512, SUPGRAM_SMEM_FLOATS * sizeof(float), st>>>(
+                    c.sc, c.X, p.panel_stride, p.batch_stride, p.ns, D, E, p.m_pad, p.m_pad, p.rows_per_wg_q, v3.Qfin, v3.subact, v3.Din, Gx6, c.done, c.nupd, p.npairs_s);
+            else
+                supdate_split_kernel<<<dim3(p.nchunks_s, p.npairs_s, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.ns, D, p.m_pad,
+                                                                                        p.rows_per_wg_s, v3.Qfin, v3.subact, c.done, c.nupd);
+        }
+    }
+    return ASVD_OK;
+}
+
+// per-problem state of the sweeps: what info_host reports; done mirrors the device's done flags
+struct Progress {
+    std::vector<int> status, sweeps, last_rot, done;
+    std::vector<float> last_off, prev_off;
+    explicit Progress(int batch)
+        : status(batch, ASVD_N_NOCONV), sweeps(batch, 0), last_rot(batch, 0), done(batch, 0), last_off(batch, 0.0f), prev_off(batch, 1e30f) {}
+};
+
+// Profile and ASVD_DEBUG record of the sweep just done, over the problems that were still running in it.
+// flags: [maxoff bits | nrot | done | super-pair updates] x batch, as read back after the sweep.
+static void note_sweep(const Plan& p, const Progress& pr, const std::vector<int>& flags, int sweep, bool sparse, long long marked, double ms) {
+    const int batch = p.batch;
+    long long rot = 0, upd = 0, running = 0;
+    for (int b = 0; b < batch; ++b)
+        if (!pr.done[b]) { rot += flags[batch + b]; upd += flags[3 * batch + b]; ++running; }
+    if (g_prof.on) {
+        g_prof.sweep_ms.push_back((float)ms);
+        g_prof.sweep_rot.push_back(rot);
+        g_prof.pairs[0] += sparse ? marked : running * ((long long)p.nb * (p.nb - 1) / 2);
+        g_prof.pairs[1] += rot;
+        g_prof.pairs[2] += upd;
+    }
+    debug_trace("sweep %d%s wall %.2f ms, rotated pairs (all problems) %lld, marked %lld", sweep + 1, sparse ? " (sparse)" : "", ms, rot, marked);
+}
+
+// The convergence rules, per problem still running, from the flags of the sweep just done.  Returns true when every problem has finished;
+// *changed: a problem finished in this sweep.
+static bool update_convergence(Progress& pr, const std::vector<int>& flags, int sweep, float tol, bool* changed) {
+    const int batch = (int)pr.done.size();
+    bool all_done = true;
+    for (int b = 0; b < batch; ++b) {
+        if (pr.done[b]) continue;
+        float mo;
+        const unsigned bits = (unsigned)flags[b];
+        std::memcpy(&mo, &bits, sizeof(float));
+        pr.sweeps[b] = sweep + 1;
+        pr.last_rot[b] = flags[batch + b];
+        pr.last_off[b] = mo;
+        debug_trace("b=%d sweep=%d maxoff=%.3e rotated_pairs=%d", b, sweep + 1, mo, pr.last_rot[b]);
+        bool finished = true;
+        if (mo != mo) pr.status[b] = ASVD_N_NAN;
+        // Jacobi converges quadratically: a sweep that STARTED with max |cos| = mo leaves ~mo^2 behind, so a sweep with
+        // mo < 0.3 sqrt(tol) has already produced orthogonality below tol (pairs above tol were all rotated in it).
+        else if (mo < tol || mo < 0.3f * sqrtf(tol)) pr.status[b] = ASVD_OK;
+        // stagnation at the fp32 noise floor: the scaled off-diagonal stopped contracting well below the level that
+        // matters for the 1e-4 sigma / 1e-3 reconstruction contract (second-order in maxoff) -> converged
+        else if (mo < 100.0f * tol && mo > 0.25f * pr.prev_off[b]) pr.status[b] = ASVD_OK;
+        else finished = all_done = false;
+        if (finished) { pr.done[b] = 1; *changed = true; }
+        pr.prev_off[b] = mo;
+    }
+    return all_done;
+}
+
+// the next sweep is sparse once fewer than half of the pairs of the still-running problems rotated in this one
+static bool next_sweep_sparse(const Plan& p, const Progress& pr) {
+    if (p.nb < 8) return false;
+    long long rot = 0, tot = 0;
+    for (int b = 0; b < p.batch; ++b)
+        if (!pr.done[b]) { rot += pr.last_rot[b]; tot += (long long)p.nb * (p.nb - 1) / 2; }
+    return tot > 0 && (double)rot < 0.5 * (double)tot;
+}
+
+// Backsolve (right vectors), column norms, ranks, the k leading columns gathered into the outputs; info_host filled.  Returns the worst status.
+static int direct_finalize(const Direct& c, const Progress& pr, float* const* U_host, float* const* S_host, float* const* V_host, int64_t k,
+                           int* info_host) {
+    const Plan& p = c.p; const int batch = p.batch; const hipStream_t st = c.st;
+    {
+        ProfScope ps(4, st);
+        if (p.vmode == 2) {
+            const int64_t ops = (int64_t)p.m_pad * PB;
+            backsolve_kernel<<<dim3((unsigned)ceil_div64(p.nb, 4), (unsigned)ceil_div64(p.nb, 4), batch), 256, 0, st>>>(
+                (const float*)(c.wb + p.off_xorig), ops, ops * p.nb, c.X, p.panel_stride, p.batch_stride, p.nb, p.m_pad);
+        }
+        colnorm_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(c.X, p.panel_stride, p.batch_stride, p.m_pad, p.R, p.n_pad, c.sig, c.ina, c.inv);
+        rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(c.sig, p.n_pad, c.perm);
+        for (int b = 0; b < batch; ++b) {
+            float* Uo = U_host ? U_host[b] : nullptr;
+            float* Vo = V_host ? V_host[b] : nullptr;
+            // oriented left vectors (A part) are U of A when not transposed, V of A when transposed
+            float* outA = p.transposed ? Vo : Uo;
+            float* outV = p.transposed ? Uo : Vo;
+            const int rowsA = outA ? p.rows : 0;
+            const int rowsV = (p.vmode != 0 && outV) ? p.cols : 0;   // V rows exist only when the right vectors were requested
+            dim3 grid((unsigned)ceil_div64(k, 64), (unsigned)ceil_div64(rowsA + rowsV > 0 ? rowsA + rowsV : 1, 64));
+            gather_kernel<<<grid, 256, 0, st>>>(c.X + (int64_t)b * p.batch_stride, p.panel_stride, p.m_pad, p.R,
+                                                c.sig + (int64_t)b * p.n_pad, c.ina + (int64_t)b * p.n_pad,
+                                                c.inv + (int64_t)b * p.n_pad, c.perm + (int64_t)b * p.n_pad, rowsA, rowsV,
+                                                (int)k, outA, outV, S_host[b]);
+        }
+    }
+    ASVD_HIP_CHECK(hipStreamSynchronize(st));
+    ASVD_HIP_CHECK(hipGetLastError());
+
+    int worst = ASVD_OK;
+    for (int b = 0; b < batch; ++b) {
+        if (info_host) {
+            info_host[4 * b + 0] = pr.status[b];
+            info_host[4 * b + 1] = pr.sweeps[b];
+            info_host[4 * b + 2] = pr.last_rot[b];
+            std::memcpy(&info_host[4 * b + 3], &pr.last_off[b], sizeof(float));  // last sweep's max scaled off-diagonal (float bits)
+        }
+        if (pr.status[b] > worst) worst = pr.status[b];
+    }
+    return worst;
+}
+
+// One direct call; its arguments are those asvd_svd_batched has checked.  allow_f16: the fused update + Gram kernel of the dense sweeps
+// (split-fp16 arithmetic with power-of-two column scales taken from the carried column norms, twolevel.h).  When a problem turned NaN on that
+// path nothing is finalised: the call is repeated with the separate passes (fp32 Gram pass, split-bf16 update pass), which need no scales — a
+// NaN that is in the data comes back as NaN.
+static int svd_direct(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
+                      const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
+                      float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
+                      int* info_host, void* stream, bool allow_f16 = true) {
+    Direct c;
+    // the right vectors of the oriented problem are V of A (not transposed) or U of A (transposed)
+    if (int rc = make_plan(batch, m, n, (m < n ? U_host : V_host) != nullptr, c.p)) return rc;
+    if (work_bytes < c.p.total) return ASVD_E_WORKSPACE;
+    if (max_sweeps <= 0) max_sweeps = 30;
+    if (!(tol > 0.0f)) tol = 1e-6f;
+    direct_bind(c, work, (hipStream_t)stream, k, tol);
+    const Plan& p = c.p;
+    if (int rc = direct_pack(c, a_host, a_dtype, lda, cs_host, cs_dtype)) return rc;
+
+    // a two-level dense sweep runs only its internal step d = 1 through the single-level kernels (it also refreshes the carried diagonal
+    // blocks); its super-steps follow
+    const std::vector<int> steps = p.two ? std::vector<int>{0} : single_level_schedule(c.nsteps);
+    std::vector<int> flags((size_t)batch * 4, 0);
+    Progress pr(batch);
+    SparseLists sl;
+    bool sparse = false, fused_used = false;
+    for (int sweep = 0; sweep < max_sweeps; ++sweep) {
+        const auto t0 = std::chrono::steady_clock::now();
+        ASVD_HIP_CHECK(hipMemsetAsync(c.maxoff, 0, (size_t)batch * sizeof(int), c.st));
+        ASVD_HIP_CHECK(hipMemsetAsync(c.nrot, 0, (size_t)batch * sizeof(int), c.st));
+        ASVD_HIP_CHECK(hipMemsetAsync(c.nupd, 0, (size_t)batch * sizeof(int), c.st));
+        long long marked = 0;
+        if (sparse) {
+            if (int rc = sparse_snapshot(c, pr.done, sl, &marked, t0)) return rc;
+            sparse_rounds(c, sl);
+        } else {
+            single_level_steps(c, steps, p.two);
+            if (int rc = p.two ? super_steps(c, allow_f16, &fused_used) : ASVD_OK) return rc;
+        }
+        ASVD_HIP_CHECK(hipMemcpyAsync(flags.data(), c.wb + p.off_flags, (size_t)batch * 4 * sizeof(int), hipMemcpyDeviceToHost, c.st));
+        ASVD_HIP_CHECK(hipStreamSynchronize(c.st));
+        note_sweep(p, pr, flags, sweep, sparse, marked, ms_since(t0));
+        bool changed = false;
+        if (update_convergence(pr, flags, sweep, c.tol, &changed)) break;
+        sparse = next_sweep_sparse(p, pr);
+        if (changed) {
+            ASVD_HIP_CHECK(hipMemcpyAsync(c.done, pr.done.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, c.st));
+            ASVD_HIP_CHECK(hipStreamSynchronize(c.st));  // pr.done may be modified next sweep
+        }
+    }
+
+    for (int b = 0; b < batch && fused_used; ++b)
+        if (pr.status[b] == ASVD_N_NAN) {
+            debug_trace("problem %d turned NaN on the split-fp16 path: repeating the call with the separate passes", b);
+            g_last_path |= ASVD_PATH_PLAIN_RETRY;
+            return svd_direct(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
+                              stream, false);
+        }
+    return direct_finalize(c, pr, U_host, S_host, V_host, k, info_host);
+}
+
+static bool nn_i8_wanted() {
+    const char* e = getenv("ASVD_NN_I8");   // read per call
+    return !(e && atoi(e) == 0);
+}
+static bool gram_i8_wanted() {
+    const char* e = getenv("ASVD_GRAM_I8");   // read per call: tests and A/B runs toggle it inside one process
+    return !(e && atoi(e) == 0);
+}
+
+// G (upper 32-blocks) = X^T X of the packed panels through the int8 digit planes (gram_i8.h).  scratch: >= 3 * n_pad * 64 * batch bytes; the
+// rows go in segments of what fits (and of at most 32768 rows: the int32 accumulators), each added to G in fp64.  ex: n_pad column exponents per
+// problem (colmaxexp_kernel) in the order of X.  inv / exs / dp (all or none): column q of X goes to plane position inv[q], exs / dp are the exponents and
+// norms in plane order, and G_ij / (dp_i dp_j) is stored — the sorted, unit-scaled Gram matrix the Cholesky factorisation starts from, without a pass
+// over an unsorted one.
+static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_stride, int nb, int m_pad, int n_pad, int batch, double* G,
+                          int64_t ldg, int64_t gbs, signed char* scratch, size_t scratch_bytes, const int* ex, const int* inv, const int* exs,
+                          const double* dp, int seg_rows_max, hipStream_t st) {
+    int64_t cap_rows = (int64_t)(scratch_bytes / ((size_t)3 * n_pad * batch)) / 64 * 64;
+    if (cap_rows > 32768) cap_rows = 32768;
+    if (seg_rows_max >= 64 && cap_rows > seg_rows_max / 64 * 64) cap_rows = seg_rows_max / 64 * 64;
+    if (cap_rows < 64) return ASVD_E_WORKSPACE;
+    const int64_t m64 = round_up64(m_pad, 64);
+    const int nseg = (int)ceil_div64(m64, cap_rows);
+    const int seg = (int)round_up64(ceil_div64(m64, nseg), 64);
+    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)gram_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
+    const int nt = (nb + 3) / 4, ntri = nt * (nt + 1) / 2;
+    for (int s = 0; s < nseg; ++s) {
+        const int r0 = s * seg;
+        const int rows = (int)std::min<int64_t>(seg, m64 - r0);
+        if (rows <= 0) break;
+        const int kgs = rows / 16;
+        const int64_t plane_stride = (int64_t)nb * kgs * 512;
+        split_i8_kernel<<<dim3(nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(Xp, panel_stride, batch_stride, nb, m_pad, n_pad, ex, r0, kgs,
+                                                                                       scratch, plane_stride, inv, nullptr);
+        gram_i8_kernel<<<dim3(ntri, batch), 512, 2 * GI_STAGE_BYTES, st>>>(scratch, plane_stride, nb, kgs, n_pad, inv ? exs : ex, G, ldg, gbs, s > 0 ? 1 : 0, nt,
+                                                                           dp);
+    }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+struct TallLayout {
+    size_t off_xp, off_g, off_gs, off_dp, off_df, off_perm, off_dg, off_d, off_fail, off_r, off_vr, off_part, off_inv, off_bex, off_aex, off_vmax, off_gex, off_ex, off_exs, off_cinv, off_inner, inner_bytes, total;
+    int n_pad64;
+};
+
+static int tall_layout(int batch, const Plan& p, int want_vectors, int64_t k, TallLayout& t) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    t.n_pad64 = p.n_pad;  // n_pad is a multiple of 64 = Cholesky block
+    t.off_xp = take((size_t)p.m_pad * PB * p.nb * batch * sizeof(float));
+    t.off_g = take((size_t)p.n_pad * p.n_pad * batch * sizeof(double));
+    t.off_gs = take((size_t)p.n_pad * p.n_pad * batch * sizeof(double));
+    t.off_dp = take((size_t)p.n_pad * batch * sizeof(double));
+    t.off_df = take((size_t)p.n_pad * batch * sizeof(float));
+    t.off_perm = take((size_t)p.n_pad * batch * sizeof(int));
+    t.off_dg = take((size_t)(p.n_pad / CB) * CB * CB * batch * sizeof(double));
+    t.off_d = take((size_t)p.n_pad * batch * sizeof(double));
+    t.off_fail = take((size_t)batch * sizeof(int));
+    t.off_r = take((size_t)p.n_pad * p.n_pad * batch * sizeof(float));
+    t.off_vr = take(want_vectors ? (size_t)2 * p.cols * k * batch * sizeof(float) : 0);  // permuted + un-permuted right vectors
+    t.off_part = take(want_vectors ? (size_t)64 * k * batch * sizeof(double) : 0);  // per problem: the epilogues run on side streams
+    t.off_inv = take(want_vectors ? (size_t)k * batch * sizeof(float) : 0);
+    // column exponents of the int8 Gram matrix (gram_i8.h), original and sorted order
+    t.off_ex = take((size_t)p.n_pad * batch * sizeof(int));
+    t.off_exs = take((size_t)p.n_pad * batch * sizeof(int));
+    t.off_cinv = take((size_t)p.n_pad * batch * sizeof(int));   // plane position of every column (inverse of the norm sort)
+    // exponents of the int8 long-side product (nn_gemm_i8.h): columns of X, rows of X, columns of Vr (key of the maximum, then the exponent)
+    t.off_bex = take(want_vectors ? (size_t)p.n_pad * batch * sizeof(int) : 0);
+    t.off_aex = take(want_vectors ? (size_t)round_up64(p.m_pad, 128) * batch * sizeof(int) : 0);
+    t.off_vmax = take(want_vectors ? (size_t)round_up64(k, 32) * batch * sizeof(unsigned) : 0);
+    t.off_gex = take(want_vectors ? (size_t)round_up64(k, 32) * batch * sizeof(int) : 0);
+    Plan pi;
+    int rc = make_plan(batch, p.cols, p.cols, want_vectors, pi);
+    if (rc) return rc;
+    t.inner_bytes = pi.total;
+    t.off_inner = take(pi.total);
+    t.total = off;
+    return ASVD_OK;
+}
+
+static size_t tall_worksize(int batch, int64_t m, int64_t n, int want_vectors, int64_t k) {
+    Plan p;
+    if (make_plan(batch, m, n, 0, p)) return 0;
+    TallLayout t;
+    if (tall_layout(batch, p, want_vectors, k, t)) return 0;
+    return t.total;
+}
+
+
+// Y = X Vr for the problems [b0, b0 + zb) of the epilogue on the int8 matrix pipe (nn_gemm_i8.h).  Digit planes: Vr in the G region, X^T (row
+// segments of what fits) in the Gs region — both free since R left them; exponents in their own small arrays.
+static int launch_nn_i8(const Plan& p, const TallLayout& t, char* wb, const TallBatch& tb, int b0, int zb, int64_t k, hipStream_t st) {
+    const float* Xz = (const float*)(wb + t.off_xp) + (int64_t)b0 * p.batch_stride;
+    const double* d = (const double*)(wb + t.off_d);
+    int* bex = (int*)(wb + t.off_bex) + (int64_t)b0 * p.n_pad;
+    const int rows_pad = (int)round_up64(p.m_pad, 128), kp = (int)round_up64(k, 32);
+    int* aex = (int*)(wb + t.off_aex) + (int64_t)b0 * rows_pad;
+    unsigned* vmax = (unsigned*)(wb + t.off_vmax) + (int64_t)b0 * kp;
+    int* gex = (int*)(wb + t.off_gex) + (int64_t)b0 * kp;
+    const int cgs = p.n_pad / 16, jps = kp / 32;
+    const int64_t strideB = (int64_t)jps * cgs * 512;
+    signed char* planesB = (signed char*)(wb + t.off_g);
+    signed char* planesA = (signed char*)(wb + t.off_gs);
+    colexp_from_norm_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * zb, 256), 256, 0, st>>>(d + (int64_t)b0 * p.n_pad, p.n_pad * zb, bex);
+    rowmaxexp_kernel<<<dim3((unsigned)(rows_pad / 8), zb), 256, 0, st>>>(Xz, p.panel_stride, p.batch_stride, p.nb, p.rows, rows_pad, bex, p.n_pad, aex);
+    ASVD_HIP_CHECK(hipMemsetAsync(vmax, 0, (size_t)kp * zb * sizeof(unsigned), st));
+    const int vchunks = (int)std::min<int64_t>(32, ceil_div64(p.cols, 64));
+    const int vrpc = (int)ceil_div64(p.cols, vchunks);
+    vcolmax_kernel<<<dim3((unsigned)ceil_div64(k, 256), vchunks, zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vrpc, vmax, kp);
+    split_v_i8_kernel<<<dim3(jps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vmax, kp, cgs, planesB, strideB, gex);
+    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)nn_gemm_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
+    int64_t seg = ((int64_t)8 * p.n_pad / 3) / 128 * 128;   // rows of X^T planes per problem that fit the Gs region
+    if (seg > rows_pad) seg = rows_pad;
+    for (int64_t r0 = 0; r0 < rows_pad; r0 += seg) {
+        const int rps = (int)(std::min<int64_t>(seg, rows_pad - r0) / 32);
+        const int64_t strideA = (int64_t)rps * cgs * 512;
+        split_xt_i8_kernel<<<dim3(rps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(Xz, p.panel_stride, p.batch_stride, p.rows, rows_pad, bex, p.n_pad,
+                                                                                      aex, (int)r0, cgs, planesA, strideA);
+        const int gx = (int)ceil_div64(jps, 4), gy = (int)ceil_div64(rps, 4);
+        nn_gemm_i8_kernel<<<dim3(gx * gy, zb), 512, 2 * GI_STAGE_BYTES, st>>>(tb, planesA, strideA, rps, planesB, strideB, jps, cgs, aex, rows_pad, gex, kp,
+                                                                             (int)r0, p.rows, (int)k, k, gx, gy);
+    }
+    return ASVD_OK;
+}
+
+// The reduction of the tall path: pack, G = X^T X, columns sorted by decreasing norm, sorted Cholesky-QR.  Leaves R (fp32) at t.off_r, the
+// column order at t.off_perm and the column norms at t.off_d.  NOT_APPLICABLE when the Cholesky breaks down.
+static int tall_reduce(const Plan& p, const TallLayout& t, char* wb, const void* const* a_host, int a_dtype, int64_t lda, const void* const* cs_host,
+                       int cs_dtype, hipStream_t st) {
+    const int batch = p.batch;
+    float* Xp = (float*)(wb + t.off_xp);
+    double *G = (double*)(wb + t.off_g), *Gs = (double*)(wb + t.off_gs), *d = (double*)(wb + t.off_d), *Dg = (double*)(wb + t.off_dg), *dp = (double*)(wb + t.off_dp);
+    float* dF = (float*)(wb + t.off_df);
+    int* cperm = (int*)(wb + t.off_perm);
+    int* fail = (int*)(wb + t.off_fail);
+    float* R = (float*)(wb + t.off_r);
+    const int64_t ldg = p.n_pad, gbs = (int64_t)p.n_pad * p.n_pad;
+    const int nbk = p.n_pad / CB;
+    {
+        ProfScope ps(0, st);
+        ASVD_HIP_CHECK(hipMemsetAsync(Xp, 0, (size_t)p.batch_stride * batch * sizeof(float), st));
+        ASVD_HIP_CHECK(hipMemsetAsync(fail, 0, (size_t)batch * sizeof(int), st));
+        if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, Xp, st)) return prc;
+    }
+    // G = X^T X: exact integer arithmetic on the int8 matrix pipe (gram_i8.h), or the fp64 matrix instructions (ASVD_GRAM_I8=0), then
+    // sort columns by decreasing norm (stable, padding last; 14 -> 10 sweeps, unsorted saves nothing), permute + unit-scale the Gram matrix.
+    // The int8 path takes the norms from the data first (fp64, colmaxexp_kernel) and stores the sorted, scaled matrix directly: Gs = D^-1 P^T G~ P D^-1
+    // with G~ the exact Gram matrix of the digitised columns and D the norms of the original ones — diagonal 1 + O(1e-7) instead of exactly 1,
+    // which is a column scaling like any other (R is un-scaled with the same D).  Digit planes in the G region, which this path does not use.
+    // A Cholesky breakdown on the int8 path is retried ONCE with the fp64 Gram matrix before the call gives up on the reduction: the digitised columns
+    // differ from X by ~2^-25 of their largest entry, which decides the sign of a pivot only where singular values sit at the fp32 rounding level of
+    // X itself (rank n/4 + 1e-4 noise under abs_mean scaling: `profiles/r6_families.txt`) — there the exact Gram matrix of the exact X still factors.
+    std::vector<int> hfail(batch, 0);
+    bool use_i8 = gram_i8_wanted();
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        {
+            ProfScope ps(0, st);
+            if (attempt) ASVD_HIP_CHECK(hipMemsetAsync(fail, 0, (size_t)batch * sizeof(int), st));
+            if (use_i8) {
+                int* ex = (int*)(wb + t.off_ex);
+                int* exs = (int*)(wb + t.off_exs);
+                colmaxexp_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(Xp, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, ex, d);
+                d_to_float_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * batch, 256), 256, 0, st>>>(d, p.n_pad * batch, dF);
+                rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(dF, p.n_pad, cperm);
+                int* cinv = (int*)(wb + t.off_cinv);
+                perm_gather_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(ex, d, cperm, p.n_pad, exs, dp, cinv);
+                if (int rc = launch_gram_i8(Xp, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, batch, Gs, ldg, gbs, (signed char*)G,
+                                            (size_t)gbs * batch * sizeof(double), ex, cinv, exs, dp, 0, st))
+                    return rc;
+            } else {
+                gram64_kernel<<<dim3(p.nb, (unsigned)ceil_div64(p.nb, 4), batch), 256, 0, st>>>(Xp, p.panel_stride, p.batch_stride, p.nb, p.m_pad, G, ldg, gbs);
+                chol_diag_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(G, ldg, gbs, p.n_pad, d);
+                d_to_float_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * batch, 256), 256, 0, st>>>(d, p.n_pad * batch, dF);
+                rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(dF, p.n_pad, cperm);
+                g_permute_scale_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), p.n_pad, batch), 256, 0, st>>>(G, ldg, gbs, d, cperm, p.n_pad, Gs, dp);
+            }
+            // block rows in groups of six (four until round 6): inside a group each finished row updates the rest of the group's strip (K = 64), the matrix
+            // behind the group is updated once per group (K = 384)
+            // (Round 6, measured and removed — profiles/r6_chol_lookahead.txt: the chain of group g + 1 on a second, equally CU-masked stream beside the bulk
+            // of group g's trailing update, the next group's strip updated first.  Reduction 48.1-48.5 -> 52.3 ms per 32 x 4096^2: the two extra launches and
+            // event hand-overs per group cost more than the 0.5 ms chain they hide, and the trailing update loses the CUs the chain occupies.)
+            // (block rows per group, 32 x 4096^2, reduction ms: 2: 48.0 · 4: 44.4-44.6 · 5: 42.1 · 6: 42.2-42.6 · 7: 41.9 · 8: 44.9-45.2 — profiles/r6_chol_group.txt)
+            constexpr int cg = 6;
+            for (int j0 = 0; j0 < nbk; j0 += cg) {
+                const int j1 = std::min(nbk, j0 + cg);
+                for (int jb = j0; jb < j1; ++jb) {
+                    chol_diag_wave_kernel<<<batch, 64, 0, st>>>(Gs, ldg, gbs, jb, fail, Dg, nbk);
+                    if (jb + 1 < nbk) chol_trsm_kernel<<<dim3(nbk - jb - 1, batch), 256, 0, st>>>(Gs, ldg, gbs, jb);
+                    if (jb + 1 < j1) chol_syrk_kernel<<<dim3(j1 - jb - 1, nbk - jb - 1, batch), 256, 0, st>>>(Gs, ldg, gbs, jb, nbk);
+                }
+                if (j1 < nbk) chol_syrk_multi_kernel<<<dim3(nbk - j1, nbk - j1, batch), 256, 0, st>>>(Gs, ldg, gbs, j0, j1 - j0, nbk);
+            }
+            r_to_f32_t_kernel<<<dim3((unsigned)(p.n_pad / 32), (unsigned)(p.n_pad / 32), batch), 256, 0, st>>>(Gs, ldg, gbs, Dg, dp, p.n_pad, R, gbs);  // n_pad is a multiple of 64
+        }
+        ASVD_HIP_CHECK(hipMemcpyAsync(hfail.data(), fail, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
+        ASVD_HIP_CHECK(hipStreamSynchronize(st));
+        bool broke = false;
+        for (int b = 0; b < batch; ++b) broke = broke || hfail[b];
+        if (!broke) break;
+        if (use_i8 && attempt == 0) {
+            debug_trace("Cholesky breakdown on the int8 Gram matrix: once more with the fp64 Gram matrix");
+            use_i8 = false;
+            g_last_path |= ASVD_PATH_GRAM_RETRY;
+            continue;
+        }
+        break;
+    }
+    for (int b = 0; b < batch; ++b)
+        if (hfail[b]) {
+            debug_trace("Cholesky-QR breakdown for problem %d (code %d): falling back to the direct path", b, hfail[b]);
+            return NOT_APPLICABLE;
+        }
+    return ASVD_OK;
+}
+
+// The vectors of the tall path: right vectors un-permuted, long-side vectors X v / sigma, sigma refined to |X v|, up to TALL_ZB problems per
+// launch.  vperm / vr: right vectors in sorted-column / original order.
+static int tall_epilogue(const Plan& p, const TallLayout& t, char* wb, const std::vector<float*>& vperm, const std::vector<float*>& vr,
+                         float* const* U_host, float* const* S_host, float* const* V_host, int64_t k, hipStream_t st) {
+    const int batch = p.batch;
+    const float* Xp = (const float*)(wb + t.off_xp);
+    const int* cperm = (const int*)(wb + t.off_perm);
+    ProfScope ps(4, st);
+    const int nsp = (int)std::min<int64_t>(64, ceil_div64(p.rows, 256));
+    const int rps = (int)ceil_div64(p.rows, nsp);
+    for (int b0 = 0; b0 < batch; b0 += TALL_ZB) {
+        const int zb = std::min(TALL_ZB, batch - b0);
+        TallBatch tb{};
+        bool any_long = false;
+        for (int z = 0; z < zb; ++z) {
+            const int b = b0 + z;
+            tb.vperm[z] = vperm[b];
+            tb.vr[z] = vr[b];
+            tb.lng[z] = p.transposed ? (V_host ? V_host[b] : nullptr) : (U_host ? U_host[b] : nullptr);
+            tb.S[z] = S_host[b];
+            any_long = any_long || tb.lng[z];
+        }
+        row_unpermute_kernel<<<dim3((unsigned)ceil_div64(k, 256), p.cols, zb), 256, 0, st>>>(tb, cperm + (int64_t)b0 * p.n_pad, p.n_pad, p.cols, (int)k);
+        if (!any_long) continue;
+        if (nn_i8_wanted() && p.cols <= 32768) {
+            if (int rc = launch_nn_i8(p, t, wb, tb, b0, zb, k, st)) return rc;
+        } else {
+            nn_gemm_split_kernel<<<dim3((unsigned)ceil_div64(k, 128), (unsigned)ceil_div64(p.rows, 128), zb), 256, 0, st>>>(
+                tb, Xp + (int64_t)b0 * p.batch_stride, p.panel_stride, p.batch_stride, p.nb, p.rows, p.cols, k, (int)k, k);
+        }
+        // sigma_j = |X v_j| and unit left vectors
+        double* part = (double*)(wb + t.off_part) + (size_t)b0 * 64 * k;
+        float* invs = (float*)(wb + t.off_inv) + (size_t)b0 * k;
+        colsumsq_kernel<<<dim3((unsigned)ceil_div64(k, 64), nsp, zb), 256, 0, st>>>(tb, k, p.rows, (int)k, rps, part, (int64_t)64 * k);
+        colfinish_kernel<<<zb, 256, 0, st>>>(tb, part, (int64_t)64 * k, nsp, (int)k, invs);
+        colscale_kernel<<<dim3((unsigned)ceil_div64(k, 256), (unsigned)ceil_div64(p.rows, 32), zb), 256, 0, st>>>(tb, k, p.rows, (int)k, invs);
+    }
+    ASVD_HIP_CHECK(hipStreamSynchronize(st));
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+// The tall path: reduction, Jacobi on R^T (the direct driver), vectors.  NOT_APPLICABLE when the reduction is not (Cholesky breakdown, workspace):
+// the caller then runs the direct path.
+static int svd_tall(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda, const void* const* cs_host,
+                    int cs_dtype, float* const* U_host, float* const* S_host, float* const* V_host, int64_t k, int max_sweeps,
+                    float tol, void* work, size_t work_bytes, int* info_host, void* stream) {
+    Plan p;
+    int rc = make_plan(batch, m, n, 0, p);  // panels hold the A rows only
+    if (rc) return rc;
+    const int want_vectors = (U_host || V_host) ? 1 : 0;
+    TallLayout t;
+    rc = tall_layout(batch, p, want_vectors, k, t);
+    if (rc) return rc;
+    if (work_bytes < t.total) return NOT_APPLICABLE;
+    hipStream_t st = (hipStream_t)stream;
+    char* wb = (char*)work;
+    // Jacobi runs on R^T: the leading right vectors of X are then the directly rotated columns (orthogonal to 1e-6) instead of
+    // backsolved ones, which matters because the long-side vectors X v / sigma amplify the error of v by sigma_1 / sigma_j;
+    // row-scaled problems (wide layers: the activation scales sit on the long side) also need 3 fewer sweeps.
+    rc = tall_reduce(p, t, wb, a_host, a_dtype, lda, cs_host, cs_dtype, st);
+    if (rc) return rc;
+
+    // right vectors of X = right vectors of R  (left vectors of R^T): written straight to the caller's short-side output when it exists, else
+    // to the temporary
+    const int64_t gbs = (int64_t)p.n_pad * p.n_pad;
+    float* R = (float*)(wb + t.off_r);
+    float* Vr = (float*)(wb + t.off_vr);
+    std::vector<const void*> rp(batch);
+    std::vector<float*> vr(batch, nullptr), vperm(batch, nullptr);
+    for (int b = 0; b < batch; ++b) {
+        rp[b] = R + (int64_t)b * gbs;
+        if (want_vectors) {
+            float* short_out = p.transposed ? (U_host ? U_host[b] : nullptr) : (V_host ? V_host[b] : nullptr);
+            vperm[b] = Vr + (int64_t)(2 * b) * p.cols * k;                       // right vectors in sorted-column order
+            vr[b] = short_out ? short_out : Vr + (int64_t)(2 * b + 1) * p.cols * k;  // ... in the original order
+        }
+    }
+    float* const* inner_U = want_vectors ? vperm.data() : nullptr;   // left vectors of R^T = right vectors of X
+    rc = svd_direct(batch, rp.data(), ASVD_F32, p.cols, p.cols, p.n_pad, nullptr, 0, inner_U, S_host, nullptr, k, max_sweeps, tol,
+                    wb + t.off_inner, t.inner_bytes, info_host, stream);
+    if (rc < 0) return rc;
+    if (want_vectors) {
+        if (int erc = tall_epilogue(p, t, wb, vperm, vr, U_host, S_host, V_host, k, st)) return erc;
+    }
+    return rc;
 }
 
 // ---- a batch as two halves on disjoint halves of the chip --------------------------------------------------------------------------------
@@ -540,6 +1289,210 @@ static bool split_applies(int batch, int64_t m, int64_t n) {
     return batch >= 4 && std::min(m, n) >= 3072;   // measured: 4 x 4096^2 -3 %, 8: -8 %, 12: -6 %, 16: -9 %, 32: -6 %; 2048 columns: nothing
 }
 
+
+static bool reduce_wanted(int64_t m, int64_t n) {
+    // The reduction pays for every shape: for tall problems it shrinks each Jacobi step from rows x cols to cols x cols, and for all
+    // of them the norm-sorted Cholesky-QR is a preconditioner (Jacobi on R^T: 14 -> 10 sweeps at 4096^2, better orthogonality).
+    if (getenv("ASVD_NO_REDUCE")) return false;
+    return std::min(m, n) >= 128;
+}
+
+// workspace of ONE call of `batch` problems whose launches are sized for the CUs of the current thread (call_cus_now())
+static int worksize_one(int batch, int64_t m, int64_t n, int want_vectors, size_t* bytes) {
+    Plan p;
+    int rc = make_plan(batch, m, n, want_vectors, p);
+    if (rc) return rc;
+    size_t need = p.total;  // the direct path is always available as the fallback
+    if (reduce_wanted(m, n)) {
+        const size_t t = tall_worksize(batch, m, n, want_vectors, p.cols);
+        if (t > need) need = t;
+    }
+    *bytes = need;
+    return ASVD_OK;
+}
+
+// g_call_cus overridden for the life of a scope
+struct CallCusScope {
+    int saved;
+    explicit CallCusScope(int cus) : saved(g_call_cus) { g_call_cus = cus; }
+    ~CallCusScope() { g_call_cus = saved; }
+};
+
+// workspaces of the two halves of a split batch, each planned for `cus` CUs: half 0 takes h0 bytes from the start, half 1 h1 bytes from off1
+static int split_worksizes(int batch, int64_t m, int64_t n, int want_vectors, int cus, size_t* h0, size_t* h1, size_t* off1) {
+    CallCusScope cs(cus);
+    int rc = worksize_one((batch + 1) / 2, m, n, want_vectors, h0);
+    if (!rc) rc = worksize_one(batch / 2, m, n, want_vectors, h1);
+    *off1 = (*h0 + 255) & ~(size_t)255;
+    return rc;
+}
+
+// One call on one stream: the reduced path where it applies, else (or when it breaks down) the direct path.  prof_base: see Profile::end.
+static int svd_batched_one(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
+                           const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
+                           float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
+                           int* info_host, void* stream, hipEvent_t prof_base) {
+    if (g_prof.on) g_prof.begin();
+    int rc = NOT_APPLICABLE;
+    g_last_path = 0;
+    if (reduce_wanted(m, n)) {
+        rc = svd_tall(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
+                      info_host, stream);
+        g_last_path |= (rc == NOT_APPLICABLE) ? ASVD_PATH_REDUCE_FALLBACK : ASVD_PATH_REDUCED;
+    }
+    if (rc == NOT_APPLICABLE)
+        rc = svd_direct(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
+                        info_host, stream);
+    if (g_prof.on) g_prof.end(prof_base);
+    return rc;
+}
+
+// The batch as two halves (see SplitCtx): the first (batch + 1) / 2 problems on the calling thread and stream s[0], the rest on the worker
+// thread and s[1].  Returns the result of the two calls, SPLIT_REFUSED, or NOT_APPLICABLE (the workspace does not hold both halves).
+static int svd_split(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
+                     const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
+                     float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
+                     int* info_host, void* stream) {
+    SplitCtx* ss = split_ctx();
+    if (!ss) return SPLIT_REFUSED;
+    const int nb0 = (batch + 1) / 2, nb1 = batch / 2;
+    size_t h0 = 0, h1 = 0, off1 = 0;
+    if (split_worksizes(batch, m, n, (U_host || V_host) ? 1 : 0, ss->cus, &h0, &h1, &off1) || work_bytes < off1 + h1) return NOT_APPLICABLE;
+    // not when another process computes on this device, not on a caller's CU-masked stream: such a call runs as ONE call on the caller's stream
+    int dev = 0;
+    ASVD_HIP_CHECK(hipGetDevice(&dev));
+    if (split_device_shared(dev) || stream_is_cu_masked((hipStream_t)stream)) return SPLIT_REFUSED;
+
+    const bool prof = g_prof.on;
+    // everything the caller queued on its stream (weights, scale vectors) is visible to both halves
+    hipEvent_t ev;
+    ASVD_HIP_CHECK(hipEventCreateWithFlags(&ev, prof ? hipEventDefault : hipEventDisableTiming));
+    ASVD_HIP_CHECK(hipEventRecord(ev, (hipStream_t)stream));
+    ASVD_HIP_CHECK(hipStreamWaitEvent(ss->s[0], ev, 0));
+    ASVD_HIP_CHECK(hipStreamWaitEvent(ss->s[1], ev, 0));
+    hipEvent_t base = prof ? ev : nullptr;
+    int rc1 = ASVD_E_HIP, path1 = 0;
+    Profile prof1;   // the worker's record of half 1
+    {
+        std::lock_guard<std::mutex> lk(ss->m);
+        ss->job = [&]() {
+            CallCusScope cs(ss->cus);
+            g_prof.on = prof;
+            try {
+                rc1 = svd_batched_one(nb1, a_host + nb0, a_dtype, m, n, lda, cs_host ? cs_host + nb0 : nullptr, cs_dtype, U_host ? U_host + nb0 : nullptr,
+                                      S_host + nb0, V_host ? V_host + nb0 : nullptr, k, max_sweeps, tol, (char*)work + off1, h1,
+                                      info_host ? info_host + 4 * nb0 : nullptr, (void*)ss->s[1], base);
+            } catch (...) { rc1 = ASVD_E_HIP; }
+            path1 = g_last_path;
+            prof1 = std::move(g_prof);
+            g_prof = Profile{};
+        };
+        ss->has_job = true;
+        ss->job_done = false;
+    }
+    ss->cv.notify_all();
+    int rc0 = ASVD_E_HIP;
+    {
+        CallCusScope cs(ss->cus);
+        try {
+            rc0 = svd_batched_one(nb0, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, h0, info_host,
+                                  (void*)ss->s[0], base);
+        } catch (...) { rc0 = ASVD_E_HIP; }
+    }
+    {
+        std::unique_lock<std::mutex> lk(ss->m);
+        ss->cv.wait(lk, [&] { return ss->job_done; });
+    }
+    g_last_path |= path1 | ASVD_PATH_SPLIT;
+    (void)hipStreamSynchronize(ss->s[0]);
+    (void)hipStreamSynchronize(ss->s[1]);
+    if (prof) {   // the halves one by one, their sums as the call's profile
+        g_split_prof.last = true;
+        for (int h = 0; h < 2; ++h) {
+            std::memcpy(g_split_prof.ms[h], (h ? prof1 : g_prof).ms, sizeof(g_prof.ms));
+            std::memcpy(g_split_prof.launches[h], (h ? prof1 : g_prof).launches, sizeof(g_prof.launches));
+        }
+        g_prof.add(prof1);
+        class8_overlap(g_prof.iv8, prof1.iv8, g_split_prof.overlap);
+    }
+    (void)hipEventDestroy(ev);
+    if (rc0 < 0) return rc0;
+    if (rc1 < 0) return rc1;
+    return std::max(rc0, rc1);
+}
+
+static int svd_batched_entry(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
+                             const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
+                             float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
+                             int* info_host, void* stream) {
+    if (!a_host || !S_host || !work || !dtype_ok(a_dtype) || lda < n) return ASVD_E_BADARG;
+    if (cs_host && !dtype_ok(cs_dtype)) return ASVD_E_BADARG;
+    if (batch < 1 || m < 1 || n < 1 || m > MAX_DIM || n > MAX_DIM) return ASVD_E_BADARG;
+    if (k < 1 || k > std::min(m, n)) return ASVD_E_BADARG;
+    for (int b = 0; b < batch; ++b)
+        if (!a_host[b] || !S_host[b]) return ASVD_E_BADARG;
+    {
+        int dev0 = 0;
+        if (hipGetDevice(&dev0) == hipSuccess) presence_register(dev0);
+    }
+    // two halves on disjoint halves of the chip (see SplitCtx above)
+    g_split_prof.last = false;
+    if (split_applies(batch, m, n) && (!g_prof.on || g_prof_keep_split) && g_call_cus == 0) {
+        const int rc = svd_split(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
+                                 info_host, stream);
+        if (rc == SPLIT_REFUSED) {
+            const int rcu = svd_batched_one(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work,
+                                            work_bytes, info_host, stream, nullptr);
+            g_last_path |= ASVD_PATH_SPLIT_REFUSED;
+            return rcu;
+        }
+        if (rc != NOT_APPLICABLE) return rc;
+    }
+    return svd_batched_one(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
+                           stream, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+void asvd_svd_set_profiling(int enabled) { g_prof.on = enabled != 0; g_prof_keep_split = enabled == 2; }
+
+int asvd_svd_get_profile(float* ms_host, int* launches_host) {
+    if (!ms_host || !launches_host) return ASVD_E_BADARG;
+    for (int i = 0; i < NPROF; ++i) { ms_host[i] = g_prof.ms[i]; launches_host[i] = g_prof.launches[i]; }
+    return ASVD_OK;
+}
+
+int asvd_svd_get_split_profile(float* ms_host, int* launches_host, float* overlap_host) {
+    if (!ms_host || !launches_host || !overlap_host) return ASVD_E_BADARG;
+    for (int h = 0; h < 2; ++h)
+        for (int i = 0; i < NPROF; ++i) { ms_host[h * NPROF + i] = g_split_prof.ms[h][i]; launches_host[h * NPROF + i] = g_split_prof.launches[h][i]; }
+    for (int i = 0; i < 4; ++i) overlap_host[i] = g_split_prof.overlap[i];
+    return g_split_prof.last ? 1 : 0;
+}
+
+int asvd_svd_get_sweep_times(float* ms_host, long long* rotated_host, int cap) {
+    const int n = (int)g_prof.sweep_ms.size();
+    for (int i = 0; i < n && i < cap; ++i) {
+        if (ms_host) ms_host[i] = g_prof.sweep_ms[i];
+        if (rotated_host) rotated_host[i] = g_prof.sweep_rot[i];
+    }
+    return n;
+}
+
+int asvd_svd_get_pair_counts(long long* counts_host) {
+    if (!counts_host) return ASVD_E_BADARG;
+    std::memcpy(counts_host, g_prof.pairs, sizeof(g_prof.pairs));
+    return ASVD_OK;
+}
+
+int asvd_svd_get_last_path(void) { return g_last_path; }
+
+// CUs the calls of THIS host thread may use (0 = the whole device): a caller that runs asvd_svd_batched on a CU-masked stream of its own says so
+// here, so that the launch geometry (row splits, chunk counts, launch forms) is sized for those CUs; such calls are never split again.
+void asvd_svd_set_call_cus(int cus) { g_call_cus = cus > 0 ? cus : 0; }
+
 void asvd_svd_set_split(int mode) { g_split_mode.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }
 
 int asvd_svd_worksize(int batch, int64_t m, int64_t n, int want_vectors, size_t* bytes) {
@@ -548,736 +1501,43 @@ int asvd_svd_worksize(int batch, int64_t m, int64_t n, int want_vectors, size_t*
     int rc = worksize_one(batch, m, n, want_vectors, &need);
     if (rc) return rc;
     if (split_applies(batch, m, n)) {   // room for the two halves, each planned for half of the CUs
-        const int saved = g_call_cus;
-        g_call_cus = std::max(1, device_cus() / 2);
-        size_t h0 = 0, h1 = 0;
-        rc = worksize_one((batch + 1) / 2, m, n, want_vectors, &h0);
-        if (!rc) rc = worksize_one(batch / 2, m, n, want_vectors, &h1);
-        g_call_cus = saved;
+        size_t h0 = 0, h1 = 0, off1 = 0;
+        rc = split_worksizes(batch, m, n, want_vectors, std::max(1, device_cus() / 2), &h0, &h1, &off1);
         if (rc) return rc;
-        need = std::max(need, ((h0 + 255) & ~(size_t)255) + h1);
+        need = std::max(need, off1 + h1);
     }
     *bytes = need;
     return ASVD_OK;
 }
 
-// Sparse sweeps: marks -> lists of disjoint pairs.  The pairs of one XOR step (I ^ J == d) are disjoint by construction, but late in the
-// iteration a step holds a handful of pairs and a sweep of nb-1 three-launch steps is all launch latency.  The marked pairs of every running
-// problem (flags: [batch][nb][nb], host_done: [batch]) are therefore packed first-fit, in schedule order (step, then I), into at most nsteps
-// ROUNDS whose pairs share no panel (per problem: a bitmask of used panels per round); a round is launched like a step.  Any order of disjoint
-// rotations is a valid Jacobi sweep; first-fit keeps the nearest-neighbour-first order of the XOR schedule among conflicting pairs.
-// list: cnt[r] slots per problem for round r from off[r] on (code I << 16 | J, -1 = empty slot).  Returns the number of marked pairs.
-static long long pack_marked_pairs(const std::vector<unsigned char>& flags, const std::vector<int>& host_done, int nb, int nsteps,
-                                   std::vector<int>& list, std::vector<int>& off, std::vector<int>& cnt) {
-    const int batch = (int)host_done.size();
-    long long marked_total = 0;
-    list.clear();
-    std::vector<std::vector<int>> tmp((size_t)batch * nsteps);  // [b * nsteps + round]
-    const int words = (nb + 63) / 64;
-    std::vector<uint64_t> used;  // [round][words] of the problem being packed
-    for (int b = 0; b < batch; ++b) {
-        if (host_done[b]) continue;
-        const unsigned char* f = flags.data() + (size_t)b * nb * nb;
-        bool packed = true;
-        used.assign((size_t)nsteps * words, 0);
-        long long n = 0;
-        for (int d = 1; d <= nsteps && packed; ++d)
-            for (int I = 0; I < nb && packed; ++I) {
-                const int J = I ^ d;
-                if (J <= I || J >= nb || !f[(size_t)I * nb + J]) continue;
-                int r = 0;
-                for (; r < nsteps; ++r) {
-                    uint64_t* u = &used[(size_t)r * words];
-                    if (!((u[I >> 6] >> (I & 63)) & 1) && !((u[J >> 6] >> (J & 63)) & 1)) {
-                        u[I >> 6] |= 1ull << (I & 63);
-                        u[J >> 6] |= 1ull << (J & 63);
-                        break;
-                    }
-                }
-                if (r == nsteps) { packed = false; break; }  // cannot happen below ~nsteps/2 marks per panel; fall back
-                tmp[(size_t)b * nsteps + r].push_back((I << 16) | J);
-                ++n;
-            }
-        if (packed) marked_total += n;
-        else {  // one list per XOR step
-            for (int r = 0; r < nsteps; ++r) tmp[(size_t)b * nsteps + r].clear();
-            for (int I = 0; I < nb; ++I)
-                for (int J = I + 1; J < nb; ++J)
-                    if (f[(size_t)I * nb + J]) { tmp[(size_t)b * nsteps + ((I ^ J) - 1)].push_back((I << 16) | J); ++marked_total; }
-        }
+int asvd_svd_batched(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
+                     const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
+                     float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
+                     int* info_host, void* stream) {
+    try {   // the host driver allocates (std::vector): nothing may be thrown across the C boundary
+        return svd_batched_entry(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
+                                 stream);
+    } catch (...) {
+        return ASVD_E_HIP;
     }
-    for (int r = 0; r < nsteps; ++r) {
-        size_t mx = 0;
-        for (int b = 0; b < batch; ++b) mx = std::max(mx, tmp[(size_t)b * nsteps + r].size());
-        cnt[r] = (int)mx;
-        off[r] = (int)list.size();
-        for (int b = 0; b < batch; ++b) {
-            const auto& v = tmp[(size_t)b * nsteps + r];
-            for (size_t i = 0; i < mx; ++i) list.push_back(i < v.size() ? v[i] : -1);
-        }
-    }
-    return marked_total;
 }
 
-// allow_f16: the fused update + Gram kernel of the dense sweeps (split-fp16 arithmetic with power-of-two column scales taken from the carried
-// column norms, twolevel.h).  *retry_plain is set, and nothing is finalised, when a problem turned NaN on that path: the caller then repeats the
-// call with the separate passes (fp32 Gram pass, split-bf16 update pass), which need no scales — a NaN that is in the data comes back as NaN.
-static int svd_direct_run(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
-                          const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
-                          float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
-                          int* info_host, void* stream, bool manage_profile, bool allow_f16, bool* retry_plain) {
-    if (!a_host || !S_host || !work || !dtype_ok(a_dtype) || lda < n) return ASVD_E_BADARG;
-    if (cs_host && !dtype_ok(cs_dtype)) return ASVD_E_BADARG;
-    Plan p;
-    {
-        // vectors of the oriented problem: its left vectors are U of A (not transposed) or V of A (transposed)
-        const bool tr = m < n;
-        const int want_left = tr ? (V_host != nullptr) : (U_host != nullptr);
-        const int want_right = tr ? (U_host != nullptr) : (V_host != nullptr);
-        int rc0 = make_plan(batch, m, n, want_left, want_right, p);
-        if (rc0) return rc0;
-    }
-    if (k < 1 || k > p.cols) return ASVD_E_BADARG;
-    if (work_bytes < p.total) return ASVD_E_WORKSPACE;
-    for (int b = 0; b < batch; ++b)
-        if (!a_host[b] || !S_host[b]) return ASVD_E_BADARG;
-    if (max_sweeps <= 0) max_sweeps = 30;
-    if (!(tol > 0.0f)) tol = 1e-6f;
-    hipStream_t st = (hipStream_t)stream;
-
-    char* wb = (char*)work;
-    float* X = (float*)(wb + p.off_x);
-    float* Gpart = (float*)(wb + p.off_gpart);
-    float* Qbuf = (float*)(wb + p.off_q);
-    int* active = (int*)(wb + p.off_active);
-    float* sig = (float*)(wb + p.off_sig);
-    float* ina = (float*)(wb + p.off_ina);
-    float* inv = (float*)(wb + p.off_inv);
-    int* perm = (int*)(wb + p.off_perm);
-    unsigned* maxoff = (unsigned*)(wb + p.off_flags);
-    int* nrot = (int*)(wb + p.off_flags) + batch;
-    int* nupd = (int*)(wb + p.off_flags) + 3 * batch;  // instrumentation: super-pair updates of the sweep
-    int* done = (int*)(wb + p.off_flags) + 2 * batch;
-
-    if (g_prof_enabled && manage_profile) prof_begin();
-
-    // ---- pack ----
-    {
-        ProfScope ps(0, st);
-        ASVD_HIP_CHECK(hipMemsetAsync(X, 0, (size_t)p.batch_stride * batch * sizeof(float), st));
-        ASVD_HIP_CHECK(hipMemsetAsync(wb + p.off_flags, 0, (size_t)batch * 4 * sizeof(int), st));
-        if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, X, st)) return prc;
-        if (p.vmode == 2) {
-            // keep the packed original (A rows of every panel) for the final backsolve
-            ASVD_HIP_CHECK(hipMemcpy2DAsync(wb + p.off_xorig, (size_t)p.m_pad * PB * sizeof(float), X, (size_t)p.R * PB * sizeof(float),
-                                            (size_t)p.m_pad * PB * sizeof(float), (size_t)p.nb * batch, hipMemcpyDeviceToDevice, st));
-        }
-    }
-
-    // ---- sweeps ----
-    std::vector<int> flags((size_t)batch * 4, 0);
-    std::vector<int> sweeps_done(batch, 0), last_rot(batch, 0), status(batch, ASVD_N_NOCONV);
-    std::vector<int> host_done(batch, 0);
-    std::vector<float> last_off(batch, 0.0f), prev_off(batch, 1e30f);
-    const bool debug = getenv("ASVD_DEBUG") != nullptr;
-    // the call's schedule description: a kernel argument of every launch below (no process-global device state)
-    Sched sc = default_sched();
-    sc.super_order = super_grouped_for(p) ? 2 : 1;
-    if (sc.super_order == 2) set_group_table(sc, p.ns, group_bits_for(p.ns));
-    const int nsteps = 2 * p.npairs - 1;
-    // panels whose convergence is enforced: those holding the k leading columns, plus one panel of margin
-    const int kb = (int)(ceil_div64(k, PB) + 1 < p.nb ? ceil_div64(k, PB) + 1 : p.nb);
-    // one inner sweep of the 64x64 eigen-solve per visit: with the XOR schedule a second one no longer saves outer sweeps
-    // (measured 26.3 vs 25.9 SVD/s)
-    constexpr int inner_sweeps = 1;
-    int sweep = 0;
-    // Step schedule of a single-level dense sweep (XOR distances d, stored as step = d-1).  The local levels d = 1..L are run twice at the
-    // start of every sweep: the strongest couplings of the sorted, preconditioned matrix sit between neighbouring panels, and a second pass
-    // over them is cheap (L extra steps of P-1) — docs/history.md (round 1).  L = min(7, P/16 - 1): measured at 4096^2 (P = 128) 8 -> 7 sweeps, +2.4 %.
-    std::vector<int> sched;
-    {
-        const int P2 = nsteps + 1;
-        const int L = std::min(std::max(0, std::min(7, P2 / 16 - 1)), nsteps);
-        for (int d = 1; d <= L; ++d) sched.push_back(d - 1);
-        for (int st2 = 0; st2 < nsteps; ++st2) sched.push_back(st2);
-    }
-    // ---- sparse-sweep state (see fullcheck_kernel) ----
-    unsigned char* pflag = (unsigned char*)(wb + p.off_pflag);
-    int* plist_dev = (int*)(wb + p.off_plist);
-    float* dnorm = (float*)(wb + p.off_ina);  // squared column norms of the snapshot (finalize overwrites this buffer later)
-    const bool sparse_allowed = p.nb >= 8;
-    constexpr double sparse_frac = 0.5;
-    bool sparse = false;
-    std::vector<unsigned char> hflag;
-    std::vector<int> hlist;
-    std::vector<int> sl_off((size_t)(nsteps > 0 ? nsteps : 1), 0), sl_cnt((size_t)(nsteps > 0 ? nsteps : 1), 0);
-    bool fused_used = false;
-    // every exit of this function — the ASVD_HIP_CHECK returns included — closes the profile it opened
-    struct ExitGuard {
-        bool prof;
-        ~ExitGuard() { if (prof) prof_end(); }
-    } exit_guard{g_prof_enabled && manage_profile};
-    // buffers of the two-level sweeps as the kernels see them
-    EvdV3 v3{};
-    v3.ns = p.ns;
-    v3.nbpan = p.nb;
-    v3.Gd32 = (float*)(wb + p.off_gd32);
-    v3.Q0 = (float*)(wb + p.off_q0);
-    v3.D0 = (float*)(wb + p.off_d0);
-    v3.Qfin = (float*)(wb + p.off_qfin);
-    v3.subact = (int*)(wb + p.off_subact);
-    v3.Din = (float*)(wb + p.off_din);
-    float* Gx6 = (float*)(wb + p.off_gx6);
-    for (; sweep < max_sweeps; ++sweep) {
-        const auto sweep_t0 = std::chrono::steady_clock::now();
-        ASVD_HIP_CHECK(hipMemsetAsync(maxoff, 0, (size_t)batch * sizeof(int), st));
-        ASVD_HIP_CHECK(hipMemsetAsync(nrot, 0, (size_t)batch * sizeof(int), st));
-        ASVD_HIP_CHECK(hipMemsetAsync(nupd, 0, (size_t)batch * sizeof(int), st));
-        long long marked_total = 0;
-        if (sparse) {
-            // 1. snapshot of all couplings
-            {
-                ProfScope ps(5, st);
-                ASVD_HIP_CHECK(hipMemsetAsync(pflag, 0, (size_t)batch * p.nb * p.nb, st));
-                const unsigned nt = (unsigned)ceil_div64(p.nb, 4);
-                const char* es8 = getenv("ASVD_SNAP_I8");   // read per call
-                const bool snap8 = p.nb >= 8 && p.m_pad <= 32768 && !(es8 && atoi(es8) == 0);
-                if (snap8) panel_sumsq_max_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(X, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, dnorm, (int*)(wb + p.off_snapex), done);
-                else panel_sumsq_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, dnorm, done);
-                if (snap8) {
-                    // X^T X from int8 digit planes (snapshot_i8.h): digitise once, eight exact digit products per fp32 product
-                    int* sex = (int*)(wb + p.off_snapex);
-                    signed char* spl = (signed char*)(wb + p.off_snap);
-                    const int kgs = (int)(round_up64(p.m_pad, 64) / 16);
-                    const int64_t plane_stride = (int64_t)p.nb * kgs * 512;
-                    split_i8_kernel<<<dim3(p.nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, sex, 0,
-                                                                                                   kgs, spl, plane_stride, nullptr, done);
-                    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)fullcheck_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
-                    fullcheck_i8_kernel<<<dim3(nt * (nt + 1) / 2, batch), 512, 2 * GI_STAGE_BYTES, st>>>(spl, plane_stride, p.nb, kgs, p.n_pad, sex, dnorm, tol, kb,
-                                                                                                      pflag, maxoff, done, (int)nt);
-                } else {
-                    fullcheck_kernel<<<dim3(nt, nt, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, dnorm, tol, kb, pflag,
-                                                                          maxoff, done);
-                }
-            }
-            hflag.resize((size_t)batch * p.nb * p.nb);
-            ASVD_HIP_CHECK(hipMemcpyAsync(hflag.data(), pflag, hflag.size(), hipMemcpyDeviceToHost, st));
-            ASVD_HIP_CHECK(hipStreamSynchronize(st));
-            if (debug) fprintf(stderr, "[asvd_svd]   snapshot + readback %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count());
-            // 2. marks -> lists of disjoint pairs
-            marked_total = pack_marked_pairs(hflag, host_done, p.nb, nsteps, hlist, sl_off, sl_cnt);
-            if (debug) fprintf(stderr, "[asvd_svd]   lists built at %.2f ms (%zu slots)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count(), hlist.size());
-            if (!hlist.empty()) ASVD_HIP_CHECK(hipMemcpyAsync(plist_dev, hlist.data(), hlist.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        }
-        // two-level dense sweep: only the internal step d = 1 runs through the single-level kernels (it also refreshes the carried
-        // diagonal blocks); the super-steps follow below
-        const bool two_now = p.two && !sparse;
-        const int nsched = sparse ? nsteps : (two_now ? 1 : (int)sched.size());
-        for (int si = 0; si < nsched; ++si) {
-            const int step = sparse ? si : (two_now ? si : sched[si]);
-            if (sparse) {
-                const int slots = sl_cnt[step];
-                if (slots == 0) continue;  // no marked pair meets in this round
-                const int* pl = plist_dev + sl_off[step];
-                // few pairs per launch: split the rows further to fill the CUs, within the partial-Gram capacity of a problem
-                const int64_t chunks = p.m_pad / 32, cap = (int64_t)p.npairs * p.nsplit / slots;
-                int64_t ns = std::max<int64_t>(p.nsplit, ceil_div64(3 * call_cus_now(), (int64_t)slots * batch));
-                ns = std::min<int64_t>(std::min<int64_t>(ns, cap), std::min<int64_t>(chunks, 64));
-                if (ns < 1) ns = 1;
-                const int rps = (int)(ceil_div64(chunks, ns) * 32);
-                const int nsp = (int)ceil_div64(p.m_pad, rps);
-                const int64_t iters = ceil_div64(p.R_upd, 128);
-                int64_t nc = std::min<int64_t>(iters, std::max<int64_t>(1, ceil_div64(4 * call_cus_now(), (int64_t)slots * batch)));
-                const int rpw = (int)(ceil_div64(iters, nc) * 128);
-                const int nch = (int)ceil_div64(p.R_upd, rpw);
-                {
-                    ProfScope ps(6, st);
-                    gram_kernel<<<dim3(nsp, slots, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, rps, Gpart, done, pl, slots);
-                }
-                {
-                    ProfScope ps(2, st);
-                    launch_evdw0(false, slots, batch, st, sc, Gpart, nsp, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, pl, slots, EvdV3{});
-                }
-                {
-                    ProfScope ps(7, st);
-                    update_kernel<<<dim3(nch, slots, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.nb, step, p.R_upd, rpw, Qbuf, active, done, pl, slots);
-                }
-                continue;
-            }
-            {
-                ProfScope ps(6, st);
-                gram_kernel<<<dim3(p.nsplit, p.npairs, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.nb, step, p.m_pad, p.rows_per_split, Gpart,
-                                                                          done, nullptr, 0);
-            }
-            {
-                ProfScope ps(2, st);
-                if (two_now) {  // internal step: also emits the fresh carried diagonal blocks of both panels of every pair
-                    launch_evdw0(true, p.npairs, batch, st, sc, Gpart, p.nsplit, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, nullptr, 0, v3);
-                } else {
-                    launch_evdw0(false, p.npairs, batch, st, sc, Gpart, p.nsplit, Qbuf, active, maxoff, nrot, done, tol, inner_sweeps, p.nb, step, kb, nullptr, 0, EvdV3{});
-                }
-            }
-            {
-                ProfScope ps(7, st);
-                update_kernel<<<dim3(p.nchunks, p.npairs, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.nb, step, p.R_upd, p.rows_per_wg, Qbuf, active,
-                                                                             done, nullptr, 0);
-            }
-        }
-        if (two_now) {
-            const bool super_grp = super_grouped_for(p);
-            const int sgb = super_grp ? group_bits_for(p.ns) : 0, sG1 = (1 << sgb) - 1;   // grouped schedule: group size - 1
-            const int nsuper = super_grp ? grouped_steps(p.ns, sgb) : 2 * p.npairs_s - 1;
-            // supgram: the update of step D also leaves the Gram tiles of the step that follows (one pass instead of two); the stand-alone Gram
-            // pass then runs only in front of the first super-step.  ASVD_SUPGRAM=0 keeps the separate passes (fp32 Gram pass, split-bf16 update
-            // pass: also what a call falls back to when the split-fp16 path of the fused kernel turns a problem NaN).
-            const bool fuse_ug = allow_f16 && p.npairs_s >= 2 && !(getenv("ASVD_SUPGRAM") && atoi(getenv("ASVD_SUPGRAM")) == 0);
-            fused_used = fused_used || fuse_ug;
-            if (fuse_ug)
-                ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)supgram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SUPGRAM_SMEM_FLOATS * sizeof(float))));
-            // on a padded XOR schedule (ns not a power of two and no grouped schedule) many super-steps hold few real pairs and the fused kernel,
-            // which reads every panel of a quad with a present member, loses to the separate passes, which touch only the pairs that exist
-            // (13B shapes, ns = 80 in a 128-wide schedule: always fused 21.4 s, never fused 16.9 s for the model): fused on full schedules only
-            const bool ns_pow2 = (p.ns & (p.ns - 1)) == 0;
-            // (Round 5 measured a LINE-SPREAD order of the distances from a given dense sweep on — triples {d, w(d), w^2(d)} that close the four
-            // super-panels of a quad — against this one: slower from every starting sweep, profiles/r5_spread_order_from_sweep.txt; removed.)
-            for (int di = 0; di < nsuper; ++di) {
-                const int D = di + 1;
-                const int E = (di + 1 < nsuper) ? di + 2 : 0;  // 0: last super-step of the sweep
-                auto fused_after = [&](int dj) {  // does the launch of super-step index dj also leave the tiles of index dj + 1 ?
-                    if (!fuse_ug || dj < 0 || dj + 1 >= nsuper) return false;
-                    if (super_grp) {  // consecutive steps inside the groups (XOR distances 1..15), or consecutive offsets of the same round of group pairs
-                        const int s0 = dj, s1 = dj + 1;   // 0-based super-steps
-                        return s1 < sG1 || (s0 >= sG1 && ((s0 - sG1) >> sgb) == ((s1 - sG1) >> sgb));
-                    }
-                    return ns_pow2;
-                };
-                const bool gram_in = !fused_after(di - 1);   // tiles of this step not left by the previous launch
-                const bool gram_out = fused_after(di);
-                v3.nsplit6 = gram_in ? p.nsplit_s : p.nchunks_q;
-                v3.Gx6 = Gx6;
-                if (gram_in) {
-                    ProfScope ps(1, st);
-                    sgram6_kernel<<<dim3(p.nsplit_s, p.npairs_s, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.ns, D, p.m_pad, p.rows_per_split_s, Gx6, done);
-                }
-                {
-                    ProfScope ps(2, st);  // both inner steps of every super-pair in one launch, one wave per 64x64 solve (evd_wave.hip)
-                    launch_evdw12(p.npairs_s, batch, st, sc, maxoff, nrot, done, tol, inner_sweeps, p.nb, D - 1, kb, v3, p.cols >= 2048);
-                }
-                {
-                    ProfScope ps(gram_out ? 8 : 3, st);
-                    if (gram_out)
-                        supgram_kernel<<<dim3(p.nchunks_q, (2 * p.npairs_s) / 4, batch), 512, SUPGRAM_SMEM_FLOATS * sizeof(float), st>>>(
-                            sc, X, p.panel_stride, p.batch_stride, p.ns, D, E, p.R_upd, p.m_pad, p.rows_per_wg_q, v3.Qfin, v3.subact, v3.Din, Gx6, done, nupd, p.npairs_s);
-                    else
-                        supdate_split_kernel<<<dim3(p.nchunks_s, p.npairs_s, batch), 256, 0, st>>>(sc, X, p.panel_stride, p.batch_stride, p.ns, D, p.R_upd,
-                                                                                                p.rows_per_wg_s, v3.Qfin, v3.subact, done, nupd);
-                }
-            }
-        }
-        ASVD_HIP_CHECK(hipMemcpyAsync(flags.data(), wb + p.off_flags, (size_t)batch * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-        ASVD_HIP_CHECK(hipStreamSynchronize(st));
-        if (g_prof_enabled) {
-            long long rot = 0;
-            for (int b = 0; b < batch; ++b) rot += host_done[b] ? 0 : flags[batch + b];
-            g_prof_sweep_ms.push_back((float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count());
-            g_prof_sweep_rot.push_back(rot);
-        }
-        if (debug) {
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sweep_t0).count();
-            long rot = 0;
-            for (int b = 0; b < batch; ++b) rot += host_done[b] ? 0 : flags[batch + b];
-            fprintf(stderr, "[asvd_svd] sweep %d%s wall %.2f ms, rotated pairs (all problems) %ld, marked %lld\n", sweep + 1, sparse ? " (sparse)" : "", ms, rot, marked_total);
-        }
-        bool all_done = true;
-        bool changed = false;
-        for (int b = 0; b < batch; ++b) {
-            if (host_done[b]) continue;
-            float mo;
-            unsigned bits = (unsigned)flags[b];
-            std::memcpy(&mo, &bits, sizeof(float));
-            sweeps_done[b] = sweep + 1;
-            last_rot[b] = flags[batch + b];
-            if (g_prof_enabled) { g_prof_pairs[0] += sparse ? 0 : (long long)p.nb * (p.nb - 1) / 2; g_prof_pairs[1] += last_rot[b]; g_prof_pairs[2] += flags[3 * batch + b]; }
-            last_off[b] = mo;
-            if (debug) fprintf(stderr, "[asvd_svd] b=%d sweep=%d maxoff=%.3e rotated_pairs=%d\n", b, sweep + 1, mo, last_rot[b]);
-            if (mo != mo) { status[b] = ASVD_N_NAN; host_done[b] = 1; changed = true; }
-            // Jacobi converges quadratically: a sweep that STARTED with max |cos| = mo leaves ~mo^2 behind, so a sweep with
-            // mo < 0.3 sqrt(tol) has already produced orthogonality below tol (pairs above tol were all rotated in it).
-            else if (mo < tol || mo < 0.3f * sqrtf(tol)) { status[b] = ASVD_OK; host_done[b] = 1; changed = true; }
-            // stagnation at the fp32 noise floor: the scaled off-diagonal stopped contracting well below the level that
-            // matters for the 1e-4 sigma / 1e-3 reconstruction contract (second-order in maxoff) -> converged
-            else if (mo < 100.0f * tol && mo > 0.25f * prev_off[b]) { status[b] = ASVD_OK; host_done[b] = 1; changed = true; }
-            else all_done = false;
-            prev_off[b] = mo;
-        }
-        if (g_prof_enabled && sparse) g_prof_pairs[0] += marked_total;
-        if (all_done) { ++sweep; break; }
-        {
-            // the next sweep is sparse once fewer than half of the pairs of the still-running problems rotated in this one
-            long long rot = 0, tot = 0;
-            for (int b = 0; b < batch; ++b)
-                if (!host_done[b]) { rot += last_rot[b]; tot += (long long)p.nb * (p.nb - 1) / 2; }
-            sparse = sparse_allowed && tot > 0 && (double)rot < sparse_frac * (double)tot;
-        }
-        if (changed) {
-            ASVD_HIP_CHECK(hipMemcpyAsync(done, host_done.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, st));
-            ASVD_HIP_CHECK(hipStreamSynchronize(st));  // host_done may be modified next sweep
-        }
-    }
-
-    if (fused_used && retry_plain) {
-        for (int b = 0; b < batch; ++b)
-            if (status[b] == ASVD_N_NAN) {
-                if (debug) fprintf(stderr, "[asvd_svd] problem %d turned NaN on the split-fp16 path: repeating the call with the separate passes\n", b);
-                *retry_plain = true;
-                return ASVD_OK;
-            }
-    }
-
-    // ---- finalize ----
-    {
-        ProfScope ps(4, st);
-        if (p.vmode == 2) {
-            const int64_t ops = (int64_t)p.m_pad * PB;
-            backsolve_kernel<<<dim3((unsigned)ceil_div64(p.nb, 4), (unsigned)ceil_div64(p.nb, 4), batch), 256, 0, st>>>(
-                (const float*)(wb + p.off_xorig), ops, ops * p.nb, X, p.panel_stride, p.batch_stride, p.nb, p.m_pad);
-        }
-        colnorm_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(X, p.panel_stride, p.batch_stride, p.m_pad, p.R, p.n_pad, sig, ina, inv);
-        rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(sig, p.n_pad, perm);
-        for (int b = 0; b < batch; ++b) {
-            float* Uo = U_host ? U_host[b] : nullptr;
-            float* Vo = V_host ? V_host[b] : nullptr;
-            // oriented left vectors (A part) are U of A when not transposed, V of A when transposed
-            float* outA = p.transposed ? Vo : Uo;
-            float* outV = p.transposed ? Uo : Vo;
-            const int rowsA = outA ? p.rows : 0;
-            const int rowsV = (p.vmode != 0 && outV) ? p.cols : 0;   // V rows exist only when the right vectors were requested
-            dim3 grid((unsigned)ceil_div64(k, 64), (unsigned)ceil_div64(rowsA + rowsV > 0 ? rowsA + rowsV : 1, 64));
-            gather_kernel<<<grid, 256, 0, st>>>(X + (int64_t)b * p.batch_stride, p.panel_stride, p.m_pad, p.R,
-                                                sig + (int64_t)b * p.n_pad, ina + (int64_t)b * p.n_pad,
-                                                inv + (int64_t)b * p.n_pad, perm + (int64_t)b * p.n_pad, rowsA, rowsV,
-                                                (int)k, outA, outV, S_host[b]);
-        }
-    }
-    ASVD_HIP_CHECK(hipStreamSynchronize(st));
-    ASVD_HIP_CHECK(hipGetLastError());
-
-    int worst = ASVD_OK;
-    for (int b = 0; b < batch; ++b) {
-        if (info_host) {
-            info_host[4 * b + 0] = status[b];
-            info_host[4 * b + 1] = sweeps_done[b];
-            info_host[4 * b + 2] = last_rot[b];
-            std::memcpy(&info_host[4 * b + 3], &last_off[b], sizeof(float));  // last sweep's max scaled off-diagonal (float bits)
-        }
-        if (status[b] > worst) worst = status[b];
-    }
-    return worst;
+int asvd_svd(const void* a, int a_dtype, int64_t m, int64_t n, int64_t lda, const void* col_scale, int cs_dtype, float* U,
+             float* S, float* V, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes, int* info_host,
+             void* stream) {
+    const void* ap[1] = {a};
+    const void* cp[1] = {col_scale};
+    float* up[1] = {U};
+    float* sp[1] = {S};
+    float* vp[1] = {V};
+    return asvd_svd_batched(1, ap, a_dtype, m, n, lda, col_scale ? cp : nullptr, cs_dtype, (U ? up : nullptr), sp,
+                            (V ? vp : nullptr), k, max_sweeps, tol, work, work_bytes, info_host, stream);
 }
 
-static int svd_direct(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
-                      const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
-                      float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
-                      int* info_host, void* stream, bool manage_profile) {
-    bool retry = false;
-    int rc = svd_direct_run(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
-                            stream, manage_profile, true, &retry);
-    if (rc >= 0 && retry) g_last_path |= ASVD_PATH_PLAIN_RETRY;
-    if (rc >= 0 && retry)
-        rc = svd_direct_run(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
-                            stream, manage_profile, false, nullptr);
-    return rc;
-}
+}  // extern "C"
 
-
-// ---------------------------------------------------------------------------------------------------------------------
-// tall path driver (see the kernel block "Tall problems" above)
-static bool tall_wanted(const Plan& p) {
-    // The reduction pays for every shape: for tall problems it shrinks each Jacobi step from rows x cols to cols x cols, and for all
-    // of them the norm-sorted Cholesky-QR is a preconditioner (Jacobi on R^T: 14 -> 10 sweeps at 4096^2, better orthogonality).
-    if (getenv("ASVD_NO_REDUCE")) return false;
-    return p.cols >= 128;
-}
-
-static bool nn_i8_wanted() {
-    const char* e = getenv("ASVD_NN_I8");   // read per call
-    return !(e && atoi(e) == 0);
-}
-static bool gram_i8_wanted() {
-    const char* e = getenv("ASVD_GRAM_I8");   // read per call: tests and A/B runs toggle it inside one process
-    return !(e && atoi(e) == 0);
-}
-
-// G (upper 32-blocks) = X^T X of the packed panels through the int8 digit planes (gram_i8.h).  scratch: >= 3 * n_pad * 64 * batch bytes; the
-// rows go in segments of what fits (and of at most 32768 rows: the int32 accumulators), each added to G in fp64.  ex: n_pad column exponents per
-// problem (colmaxexp_kernel) in the order of X.  inv / exs / dp (all or none): column q of X goes to plane position inv[q], exs / dp are the exponents and
-// norms in plane order, and G_ij / (dp_i dp_j) is stored — the sorted, unit-scaled Gram matrix the Cholesky factorisation starts from, without a pass
-// over an unsorted one.
-static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_stride, int nb, int m_pad, int n_pad, int batch, double* G,
-                          int64_t ldg, int64_t gbs, signed char* scratch, size_t scratch_bytes, const int* ex, const int* inv, const int* exs,
-                          const double* dp, int seg_rows_max, hipStream_t st) {
-    int64_t cap_rows = (int64_t)(scratch_bytes / ((size_t)3 * n_pad * batch)) / 64 * 64;
-    if (cap_rows > 32768) cap_rows = 32768;
-    if (seg_rows_max >= 64 && cap_rows > seg_rows_max / 64 * 64) cap_rows = seg_rows_max / 64 * 64;
-    if (cap_rows < 64) return ASVD_E_WORKSPACE;
-    const int64_t m64 = round_up64(m_pad, 64);
-    const int nseg = (int)ceil_div64(m64, cap_rows);
-    const int seg = (int)round_up64(ceil_div64(m64, nseg), 64);
-    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)gram_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
-    const int nt = (nb + 3) / 4, ntri = nt * (nt + 1) / 2;
-    for (int s = 0; s < nseg; ++s) {
-        const int r0 = s * seg;
-        const int rows = (int)std::min<int64_t>(seg, m64 - r0);
-        if (rows <= 0) break;
-        const int kgs = rows / 16;
-        const int64_t plane_stride = (int64_t)nb * kgs * 512;
-        split_i8_kernel<<<dim3(nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(Xp, panel_stride, batch_stride, nb, m_pad, n_pad, ex, r0, kgs,
-                                                                                       scratch, plane_stride, inv, nullptr);
-        gram_i8_kernel<<<dim3(ntri, batch), 512, 2 * GI_STAGE_BYTES, st>>>(scratch, plane_stride, nb, kgs, n_pad, inv ? exs : ex, G, ldg, gbs, s > 0 ? 1 : 0, nt,
-                                                                           dp);
-    }
-    ASVD_HIP_CHECK(hipGetLastError());
-    return ASVD_OK;
-}
-
-struct TallLayout {
-    size_t off_xp, off_g, off_gs, off_dp, off_df, off_perm, off_dg, off_d, off_fail, off_r, off_vr, off_part, off_inv, off_bex, off_aex, off_vmax, off_gex, off_ex, off_exs, off_cinv, off_inner, inner_bytes, total;
-    int n_pad64;
-};
-
-static int tall_layout(int batch, const Plan& p, int want_vectors, int64_t k, TallLayout& t) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    t.n_pad64 = p.n_pad;  // n_pad is a multiple of 64 = Cholesky block
-    t.off_xp = take((size_t)p.m_pad * PB * p.nb * batch * sizeof(float));
-    t.off_g = take((size_t)p.n_pad * p.n_pad * batch * sizeof(double));
-    t.off_gs = take((size_t)p.n_pad * p.n_pad * batch * sizeof(double));
-    t.off_dp = take((size_t)p.n_pad * batch * sizeof(double));
-    t.off_df = take((size_t)p.n_pad * batch * sizeof(float));
-    t.off_perm = take((size_t)p.n_pad * batch * sizeof(int));
-    t.off_dg = take((size_t)(p.n_pad / CB) * CB * CB * batch * sizeof(double));
-    t.off_d = take((size_t)p.n_pad * batch * sizeof(double));
-    t.off_fail = take((size_t)batch * sizeof(int));
-    t.off_r = take((size_t)p.n_pad * p.n_pad * batch * sizeof(float));
-    t.off_vr = take(want_vectors ? (size_t)2 * p.cols * k * batch * sizeof(float) : 0);  // permuted + un-permuted right vectors
-    t.off_part = take(want_vectors ? (size_t)64 * k * batch * sizeof(double) : 0);  // per problem: the epilogues run on side streams
-    t.off_inv = take(want_vectors ? (size_t)k * batch * sizeof(float) : 0);
-    // column exponents of the int8 Gram matrix (gram_i8.h), original and sorted order
-    t.off_ex = take((size_t)p.n_pad * batch * sizeof(int));
-    t.off_exs = take((size_t)p.n_pad * batch * sizeof(int));
-    t.off_cinv = take((size_t)p.n_pad * batch * sizeof(int));   // plane position of every column (inverse of the norm sort)
-    // exponents of the int8 long-side product (nn_gemm_i8.h): columns of X, rows of X, columns of Vr (key of the maximum, then the exponent)
-    t.off_bex = take(want_vectors ? (size_t)p.n_pad * batch * sizeof(int) : 0);
-    t.off_aex = take(want_vectors ? (size_t)round_up64(p.m_pad, 128) * batch * sizeof(int) : 0);
-    t.off_vmax = take(want_vectors ? (size_t)round_up64(k, 32) * batch * sizeof(unsigned) : 0);
-    t.off_gex = take(want_vectors ? (size_t)round_up64(k, 32) * batch * sizeof(int) : 0);
-    Plan pi;
-    int rc = make_plan(batch, p.cols, p.cols, want_vectors, want_vectors, pi);
-    if (rc) return rc;
-    t.inner_bytes = pi.total;
-    t.off_inner = take(pi.total);
-    t.total = off;
-    return ASVD_OK;
-}
-
-static size_t tall_worksize(int batch, int64_t m, int64_t n, int want_vectors, int64_t k) {
-    Plan p;
-    if (make_plan(batch, m, n, 0, 0, p)) return 0;
-    TallLayout t;
-    if (tall_layout(batch, p, want_vectors, k, t)) return 0;
-    return t.total;
-}
-
-// returns ASVD_OK.., or -100 when the reduction is not applicable (Cholesky breakdown): the caller then runs the direct path
-static int svd_tall(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda, const void* const* cs_host,
-                    int cs_dtype, float* const* U_host, float* const* S_host, float* const* V_host, int64_t k, int max_sweeps,
-                    float tol, void* work, size_t work_bytes, int* info_host, void* stream) {
-    Plan p;
-    int rc = make_plan(batch, m, n, 0, 0, p);  // panels hold the A rows only
-    if (rc) return rc;
-    const int want_vectors = (U_host || V_host) ? 1 : 0;
-    TallLayout t;
-    rc = tall_layout(batch, p, want_vectors, k, t);
-    if (rc) return rc;
-    if (work_bytes < t.total) return -100;
-    hipStream_t st = (hipStream_t)stream;
-    char* wb = (char*)work;
-    float* Xp = (float*)(wb + t.off_xp);
-    double* G = (double*)(wb + t.off_g);
-    double* d = (double*)(wb + t.off_d);
-    double* Dg = (double*)(wb + t.off_dg);
-    double* Gs = (double*)(wb + t.off_gs);
-    double* dp = (double*)(wb + t.off_dp);
-    float* dF = (float*)(wb + t.off_df);
-    int* cperm = (int*)(wb + t.off_perm);
-    int* fail = (int*)(wb + t.off_fail);
-    float* R = (float*)(wb + t.off_r);
-    float* Vr = (float*)(wb + t.off_vr);
-    const int64_t ldg = p.n_pad, gbs = (int64_t)p.n_pad * p.n_pad;
-    const int nbk = p.n_pad / CB;
-    // Jacobi runs on R^T: the leading right vectors of X are then the directly rotated columns (orthogonal to 1e-6) instead of
-    // backsolved ones, which matters because the long-side vectors X v / sigma amplify the error of v by sigma_1 / sigma_j;
-    // row-scaled problems (wide layers: the activation scales sit on the long side) also need 3 fewer sweeps.
-
-    {
-        ProfScope ps(0, st);
-        ASVD_HIP_CHECK(hipMemsetAsync(Xp, 0, (size_t)p.batch_stride * batch * sizeof(float), st));
-        ASVD_HIP_CHECK(hipMemsetAsync(fail, 0, (size_t)batch * sizeof(int), st));
-        if (int prc = pack_batch(a_host, a_dtype, lda, cs_host, cs_dtype, p, Xp, st)) return prc;
-        // G = X^T X: exact integer arithmetic on the int8 matrix pipe (gram_i8.h), or the fp64 matrix instructions (ASVD_GRAM_I8=0), then
-        // sort columns by decreasing norm (stable, padding last; 14 -> 10 sweeps, unsorted saves nothing), permute + unit-scale the Gram matrix.
-        // The int8 path takes the norms from the data first (fp64, colmaxexp_kernel) and stores the sorted, scaled matrix directly: Gs = D^-1 P^T G~ P D^-1
-        // with G~ the exact Gram matrix of the digitised columns and D the norms of the original ones — diagonal 1 + O(1e-7) instead of exactly 1,
-        // which is a column scaling like any other (R is un-scaled with the same D).  Digit planes in the G region, which this path does not use.
-        // A Cholesky breakdown on the int8 path is retried ONCE with the fp64 Gram matrix before the call gives up on the reduction: the digitised columns
-        // differ from X by ~2^-25 of their largest entry, which decides the sign of a pivot only where singular values sit at the fp32 rounding level of
-        // X itself (rank n/4 + 1e-4 noise under abs_mean scaling: `profiles/r6_families.txt`) — there the exact Gram matrix of the exact X still factors.
-    }
-    std::vector<int> hfail(batch, 0);
-    bool use_i8 = gram_i8_wanted();
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        {
-        ProfScope ps(0, st);
-        if (attempt) ASVD_HIP_CHECK(hipMemsetAsync(fail, 0, (size_t)batch * sizeof(int), st));
-        if (use_i8) {
-            int* ex = (int*)(wb + t.off_ex);
-            int* exs = (int*)(wb + t.off_exs);
-            colmaxexp_kernel<<<dim3(p.nb, batch), 256, 0, st>>>(Xp, p.panel_stride, p.batch_stride, p.m_pad, p.n_pad, ex, d);
-            d_to_float_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * batch, 256), 256, 0, st>>>(d, p.n_pad * batch, dF);
-            rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(dF, p.n_pad, cperm);
-            int* cinv = (int*)(wb + t.off_cinv);
-            perm_gather_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(ex, d, cperm, p.n_pad, exs, dp, cinv);
-            rc = launch_gram_i8(Xp, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, batch, Gs, ldg, gbs, (signed char*)G,
-                                (size_t)gbs * batch * sizeof(double), ex, cinv, exs, dp, 0, st);
-            if (rc) return rc;
-        } else {
-            gram64_kernel<<<dim3(p.nb, (unsigned)ceil_div64(p.nb, 4), batch), 256, 0, st>>>(Xp, p.panel_stride, p.batch_stride, p.nb, p.m_pad, G, ldg, gbs);
-            chol_diag_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(G, ldg, gbs, p.n_pad, d);
-            d_to_float_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * batch, 256), 256, 0, st>>>(d, p.n_pad * batch, dF);
-            rank_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), batch), 256, 0, st>>>(dF, p.n_pad, cperm);
-            g_permute_scale_kernel<<<dim3((unsigned)ceil_div64(p.n_pad, 256), p.n_pad, batch), 256, 0, st>>>(G, ldg, gbs, d, cperm, p.n_pad, Gs, dp);
-        }
-        // block rows in groups of six (four until round 6): inside a group each finished row updates the rest of the group's strip (K = 64), the matrix
-        // behind the group is updated once per group (K = 384)
-        // (Round 6, measured and removed — profiles/r6_chol_lookahead.txt: the chain of group g + 1 on a second, equally CU-masked stream beside the bulk
-        // of group g's trailing update, the next group's strip updated first.  Reduction 48.1-48.5 -> 52.3 ms per 32 x 4096^2: the two extra launches and
-        // event hand-overs per group cost more than the 0.5 ms chain they hide, and the trailing update loses the CUs the chain occupies.)
-        // (block rows per group, 32 x 4096^2, reduction ms: 2: 48.0 · 4: 44.4-44.6 · 5: 42.1 · 6: 42.2-42.6 · 7: 41.9 · 8: 44.9-45.2 — profiles/r6_chol_group.txt)
-        constexpr int cg = 6;
-        for (int j0 = 0; j0 < nbk; j0 += cg) {
-            const int j1 = std::min(nbk, j0 + cg);
-            for (int jb = j0; jb < j1; ++jb) {
-                chol_diag_wave_kernel<<<batch, 64, 0, st>>>(Gs, ldg, gbs, jb, fail, Dg, nbk);
-                if (jb + 1 < nbk) chol_trsm_kernel<<<dim3(nbk - jb - 1, batch), 256, 0, st>>>(Gs, ldg, gbs, jb);
-                if (jb + 1 < j1) chol_syrk_kernel<<<dim3(j1 - jb - 1, nbk - jb - 1, batch), 256, 0, st>>>(Gs, ldg, gbs, jb, nbk);
-            }
-            if (j1 < nbk) chol_syrk_multi_kernel<<<dim3(nbk - j1, nbk - j1, batch), 256, 0, st>>>(Gs, ldg, gbs, j0, j1 - j0, nbk);
-        }
-        r_to_f32_t_kernel<<<dim3((unsigned)(p.n_pad / 32), (unsigned)(p.n_pad / 32), batch), 256, 0, st>>>(Gs, ldg, gbs, Dg, dp, p.n_pad, R, gbs);  // n_pad is a multiple of 64
-        }
-        ASVD_HIP_CHECK(hipMemcpyAsync(hfail.data(), fail, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
-        ASVD_HIP_CHECK(hipStreamSynchronize(st));
-        bool broke = false;
-        for (int b = 0; b < batch; ++b) broke = broke || hfail[b];
-        if (!broke) break;
-        if (use_i8 && attempt == 0) {
-            if (getenv("ASVD_DEBUG")) fprintf(stderr, "[asvd_svd] Cholesky breakdown on the int8 Gram matrix: once more with the fp64 Gram matrix\n");
-            use_i8 = false;
-            g_last_path |= ASVD_PATH_GRAM_RETRY;
-            continue;
-        }
-        break;
-    }
-    for (int b = 0; b < batch; ++b)
-        if (hfail[b]) {
-            if (getenv("ASVD_DEBUG")) fprintf(stderr, "[asvd_svd] Cholesky-QR breakdown for problem %d (code %d): falling back to the direct path\n", b, hfail[b]);
-            return -100;
-        }
-
-    // right vectors of X = right vectors of R  (left vectors of R^T when ASVD_RT): written straight to the caller's short-side
-    // output when it exists, else to the temporary
-    std::vector<const void*> rp(batch);
-    std::vector<float*> vr(batch, nullptr), vperm(batch, nullptr);
-    for (int b = 0; b < batch; ++b) {
-        rp[b] = R + (int64_t)b * gbs;
-        if (want_vectors) {
-            float* short_out = p.transposed ? (U_host ? U_host[b] : nullptr) : (V_host ? V_host[b] : nullptr);
-            vperm[b] = Vr + (int64_t)(2 * b) * p.cols * k;                       // right vectors in sorted-column order
-            vr[b] = short_out ? short_out : Vr + (int64_t)(2 * b + 1) * p.cols * k;  // ... in the original order
-        }
-    }
-    float* const* inner_U = want_vectors ? vperm.data() : nullptr;   // left vectors of R^T = right vectors of X
-    float* const* inner_V = nullptr;
-    rc = svd_direct(batch, rp.data(), ASVD_F32, p.cols, p.cols, p.n_pad, nullptr, 0, inner_U, S_host, inner_V, k, max_sweeps, tol,
-                    wb + t.off_inner, t.inner_bytes, info_host, stream, false);
-    if (rc < 0) return rc;
-    if (want_vectors) {
-        ProfScope ps(4, st);
-        // epilogues (un-permute, long-side product, sigma refinement), up to TALL_ZB problems per launch
-        const int nsp = (int)std::min<int64_t>(64, ceil_div64(p.rows, 256));
-        const int rps = (int)ceil_div64(p.rows, nsp);
-        for (int b0 = 0; b0 < batch; b0 += TALL_ZB) {
-            const int zb = std::min(TALL_ZB, batch - b0);
-            TallBatch tb{};
-            bool any_long = false;
-            for (int z = 0; z < zb; ++z) {
-                const int b = b0 + z;
-                tb.vperm[z] = vperm[b];
-                tb.vr[z] = vr[b];
-                tb.lng[z] = p.transposed ? (V_host ? V_host[b] : nullptr) : (U_host ? U_host[b] : nullptr);
-                tb.S[z] = S_host[b];
-                any_long = any_long || tb.lng[z];
-            }
-            row_unpermute_kernel<<<dim3((unsigned)ceil_div64(k, 256), p.cols, zb), 256, 0, st>>>(tb, cperm + (int64_t)b0 * p.n_pad, p.n_pad, p.cols, (int)k);
-            if (!any_long) continue;
-            if (nn_i8_wanted() && p.cols <= 32768) {
-                // Y = X Vr on the int8 matrix pipe (nn_gemm_i8.h).  Digit planes: Vr in the G region, X^T (row segments of what fits) in the Gs region —
-                // both free since R left them; exponents in their own small arrays.
-                const float* Xz = Xp + (int64_t)b0 * p.batch_stride;
-                int* bex = (int*)(wb + t.off_bex) + (int64_t)b0 * p.n_pad;
-                const int rows_pad = (int)round_up64(p.m_pad, 128), kp = (int)round_up64(k, 32);
-                int* aex = (int*)(wb + t.off_aex) + (int64_t)b0 * rows_pad;
-                unsigned* vmax = (unsigned*)(wb + t.off_vmax) + (int64_t)b0 * kp;
-                int* gex = (int*)(wb + t.off_gex) + (int64_t)b0 * kp;
-                const int cgs = p.n_pad / 16, jps = kp / 32;
-                const int64_t strideB = (int64_t)jps * cgs * 512;
-                signed char* planesB = (signed char*)G;
-                signed char* planesA = (signed char*)Gs;
-                colexp_from_norm_kernel<<<(unsigned)ceil_div64((int64_t)p.n_pad * zb, 256), 256, 0, st>>>(d + (int64_t)b0 * p.n_pad, p.n_pad * zb, bex);
-                rowmaxexp_kernel<<<dim3((unsigned)(rows_pad / 8), zb), 256, 0, st>>>(Xz, p.panel_stride, p.batch_stride, p.nb, p.rows, rows_pad, bex, p.n_pad, aex);
-                ASVD_HIP_CHECK(hipMemsetAsync(vmax, 0, (size_t)kp * zb * sizeof(unsigned), st));
-                const int vchunks = (int)std::min<int64_t>(32, ceil_div64(p.cols, 64));
-                const int vrpc = (int)ceil_div64(p.cols, vchunks);
-                vcolmax_kernel<<<dim3((unsigned)ceil_div64(k, 256), vchunks, zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vrpc, vmax, kp);
-                split_v_i8_kernel<<<dim3(jps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vmax, kp, cgs, planesB, strideB, gex);
-                ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)nn_gemm_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
-                int64_t seg = ((int64_t)8 * p.n_pad / 3) / 128 * 128;   // rows of X^T planes per problem that fit the Gs region
-                if (seg > rows_pad) seg = rows_pad;
-                for (int64_t r0 = 0; r0 < rows_pad; r0 += seg) {
-                    const int rps = (int)(std::min<int64_t>(seg, rows_pad - r0) / 32);
-                    const int64_t strideA = (int64_t)rps * cgs * 512;
-                    split_xt_i8_kernel<<<dim3(rps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(Xz, p.panel_stride, p.batch_stride, p.rows, rows_pad, bex, p.n_pad,
-                                                                                                  aex, (int)r0, cgs, planesA, strideA);
-                    const int gx = (int)ceil_div64(jps, 4), gy = (int)ceil_div64(rps, 4);
-                    nn_gemm_i8_kernel<<<dim3(gx * gy, zb), 512, 2 * GI_STAGE_BYTES, st>>>(tb, planesA, strideA, rps, planesB, strideB, jps, cgs, aex, rows_pad, gex, kp,
-                                                                                         (int)r0, p.rows, (int)k, k, gx, gy);
-                }
-            } else {
-                nn_gemm_split_kernel<<<dim3((unsigned)ceil_div64(k, 128), (unsigned)ceil_div64(p.rows, 128), zb), 256, 0, st>>>(
-                    tb, Xp + (int64_t)b0 * p.batch_stride, p.panel_stride, p.batch_stride, p.nb, p.rows, p.cols, k, (int)k, k);
-            }
-            // sigma_j = |X v_j| and unit left vectors
-            double* part = (double*)(wb + t.off_part) + (size_t)b0 * 64 * k;
-            float* invs = (float*)(wb + t.off_inv) + (size_t)b0 * k;
-            colsumsq_kernel<<<dim3((unsigned)ceil_div64(k, 64), nsp, zb), 256, 0, st>>>(tb, k, p.rows, (int)k, rps, part, (int64_t)64 * k);
-            colfinish_kernel<<<zb, 256, 0, st>>>(tb, part, (int64_t)64 * k, nsp, (int)k, invs);
-            colscale_kernel<<<dim3((unsigned)ceil_div64(k, 256), (unsigned)ceil_div64(p.rows, 32), zb), 256, 0, st>>>(tb, k, p.rows, (int)k, invs);
-        }
-        ASVD_HIP_CHECK(hipStreamSynchronize(st));
-        ASVD_HIP_CHECK(hipGetLastError());
-    }
-    return rc;
-}
+// ---- test hooks ----------------------------------------------------------------------------------------------------------------------------
+extern "C" {
 
 // Test hook (tests/test_gpu_twolevel.py): ONE launch of the two-level update kernel (split-bf16) on caller-built panels, so that the kernel
 // can be checked against a plain fp64 product.  X: [batch][nb][R][32] fp32 panels; Qfin: [batch][npairs][128*128]; subact: [batch][npairs][4];
@@ -1313,17 +1573,6 @@ int asvd_test_gram(const float* Xp, int64_t panel_stride, int64_t batch_stride, 
 // Test hook: the super-panel pair schedule itself.  out[step * npairs + k] = (S << 16) | T of slot k of super-step `step`, or -1 for an empty
 // slot, for the order the library would pick for `ns` super-panels (1 XOR, 2 grouped; see super_pair).  Returns the number of super-steps
 // through *nsteps_out.  tests/test_gpu_twolevel.py checks that every pair appears exactly once and that the pairs of a step are disjoint.
-}  // extern "C"
-namespace {
-__global__ void super_schedule_kernel(Sched sc, int ns, int nsteps, int npairs, int* __restrict__ out) {
-    const int step = blockIdx.x, k = threadIdx.x;
-    if (k >= npairs) return;
-    int S, T;
-    super_pair(sc, ns, step, k, S, T);
-    out[step * npairs + k] = (S < ns && T < ns) ? ((S << 16) | T) : -1;
-}
-}  // namespace
-extern "C" {
 int asvd_test_super_schedule(int ns, int grouped, int* out_dev, int out_capacity, int* nsteps_out, int* npairs_out) {
     if (ns < 2 || ns > 1024 || !out_dev || !nsteps_out || !npairs_out) return ASVD_E_BADARG;
     int pw2 = 2;
@@ -1379,183 +1628,6 @@ int asvd_test_evd_wave(const float* G, int batch, int sweeps, float* Q, float* d
     launch_evdw_test(batch, (hipStream_t)stream, G, sweeps, Q, diag, rnk, cs, Gout, meas);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
-}
-
-static int svd_batched_one(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
-                           const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
-                           float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
-                           int* info_host, void* stream) {
-    Plan p;
-    int rc = make_plan(batch, m, n, 0, 0, p);
-    if (rc) return rc;
-    if (g_prof_enabled) prof_begin();
-    rc = -100;
-    g_last_path = 0;
-    if (tall_wanted(p)) {
-        rc = svd_tall(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
-                      info_host, stream);
-        g_last_path |= (rc == -100) ? ASVD_PATH_REDUCE_FALLBACK : ASVD_PATH_REDUCED;
-    }
-    if (rc == -100)
-        rc = svd_direct(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
-                        info_host, stream, false);
-    if (g_prof_enabled) prof_end();
-    return rc;
-}
-
-static int svd_batched_entry(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
-                             const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
-                             float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
-                             int* info_host, void* stream) {
-    if (!a_host || !S_host || !work || !dtype_ok(a_dtype) || lda < n) return ASVD_E_BADARG;
-    if (cs_host && !dtype_ok(cs_dtype)) return ASVD_E_BADARG;
-    if (batch < 1 || m < 1 || n < 1) return ASVD_E_BADARG;
-    if (k < 1 || k > std::min(m, n)) return ASVD_E_BADARG;
-    for (int b = 0; b < batch; ++b)
-        if (!a_host[b] || !S_host[b]) return ASVD_E_BADARG;
-    {
-        int dev0 = 0;
-        if (hipGetDevice(&dev0) == hipSuccess) presence_register(dev0);
-    }
-    // two halves on disjoint halves of the chip (see SplitCtx above)
-    g_prof_last_split = false;
-    if (split_applies(batch, m, n) && (!g_prof_enabled || g_prof_mode == 2) && g_call_cus == 0) {
-        SplitCtx* ss = split_ctx();
-        const int want_vectors = (U_host || V_host) ? 1 : 0;
-        const int nb0 = (batch + 1) / 2, nb1 = batch / 2;
-        size_t h0 = 0, h1 = 0;
-        int rcw = ASVD_OK;
-        if (ss) {
-            g_call_cus = ss->cus;
-            rcw = worksize_one(nb0, m, n, want_vectors, &h0);
-            if (!rcw) rcw = worksize_one(nb1, m, n, want_vectors, &h1);
-            g_call_cus = 0;
-        }
-        const size_t off1 = (h0 + 255) & ~(size_t)255;
-        bool refused = !ss;
-        if (ss && !rcw && work_bytes >= off1 + h1) {
-            // not when another process computes on this device, not on a caller's CU-masked stream: such a call runs as ONE call on the caller's stream
-            int dev = 0;
-            ASVD_HIP_CHECK(hipGetDevice(&dev));
-            if (split_device_shared(dev) || stream_is_cu_masked((hipStream_t)stream)) refused = true;
-            else {
-                const bool prof = g_prof_enabled;
-                // everything the caller queued on its stream (weights, scale vectors) is visible to both halves
-                hipEvent_t ev;
-                ASVD_HIP_CHECK(hipEventCreateWithFlags(&ev, prof ? hipEventDefault : hipEventDisableTiming));
-                ASVD_HIP_CHECK(hipEventRecord(ev, (hipStream_t)stream));
-                ASVD_HIP_CHECK(hipStreamWaitEvent(ss->s[0], ev, 0));
-                ASVD_HIP_CHECK(hipStreamWaitEvent(ss->s[1], ev, 0));
-                const int cus = ss->cus;
-                int rc1 = ASVD_E_HIP, path1 = 0;
-                float ms1[NPROF] = {0};
-                int ln1[NPROF] = {0};
-                long long pairs1[3] = {0, 0, 0};
-                std::vector<std::pair<float, float>> iv1;
-                {
-                    std::lock_guard<std::mutex> lk(ss->m);
-                    ss->job = [&]() {
-                        g_call_cus = cus;
-                        g_prof_enabled = prof;
-                        g_prof_base = prof ? ev : nullptr;
-                        try {
-                            rc1 = svd_batched_one(nb1, a_host + nb0, a_dtype, m, n, lda, cs_host ? cs_host + nb0 : nullptr, cs_dtype, U_host ? U_host + nb0 : nullptr,
-                                                  S_host + nb0, V_host ? V_host + nb0 : nullptr, k, max_sweeps, tol, (char*)work + off1, h1,
-                                                  info_host ? info_host + 4 * nb0 : nullptr, (void*)ss->s[1]);
-                        } catch (...) { rc1 = ASVD_E_HIP; }
-                        path1 = g_last_path;
-                        if (prof) {
-                            for (int i = 0; i < NPROF; ++i) { ms1[i] = g_prof_ms[i]; ln1[i] = g_prof_launches[i]; }
-                            for (int i = 0; i < 3; ++i) pairs1[i] = g_prof_pairs[i];
-                            iv1.swap(g_prof_iv8);
-                        }
-                        g_call_cus = 0;
-                        g_prof_enabled = false;
-                        g_prof_base = nullptr;
-                    };
-                    ss->has_job = true;
-                    ss->job_done = false;
-                }
-                ss->cv.notify_all();
-                int rc0 = ASVD_E_HIP;
-                g_call_cus = cus;
-                g_prof_base = prof ? ev : nullptr;
-                try {
-                    rc0 = svd_batched_one(nb0, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, h0, info_host,
-                                          (void*)ss->s[0]);
-                } catch (...) { rc0 = ASVD_E_HIP; }
-                g_call_cus = 0;
-                g_prof_base = nullptr;
-                {
-                    std::unique_lock<std::mutex> lk(ss->m);
-                    ss->cv.wait(lk, [&] { return ss->job_done; });
-                }
-                g_last_path |= path1 | ASVD_PATH_SPLIT;
-                (void)hipStreamSynchronize(ss->s[0]);
-                (void)hipStreamSynchronize(ss->s[1]);
-                if (prof) {
-                    g_prof_last_split = true;
-                    for (int i = 0; i < NPROF; ++i) {
-                        g_prof_half_ms[0][i] = g_prof_ms[i]; g_prof_half_launches[0][i] = g_prof_launches[i];
-                        g_prof_half_ms[1][i] = ms1[i]; g_prof_half_launches[1][i] = ln1[i];
-                        g_prof_ms[i] += ms1[i]; g_prof_launches[i] += ln1[i];
-                    }
-                    for (int i = 0; i < 3; ++i) g_prof_pairs[i] += pairs1[i];
-                    // class 8 of both halves on one time axis: summed durations, union, and the time both halves were inside such a launch
-                    std::vector<std::pair<float, int>> edges;
-                    float sum0 = 0, sum1 = 0;
-                    for (auto& iv : g_prof_iv8) { edges.emplace_back(iv.first, +1); edges.emplace_back(iv.second, -1); sum0 += iv.second - iv.first; }
-                    for (auto& iv : iv1) { edges.emplace_back(iv.first, +1); edges.emplace_back(iv.second, -1); sum1 += iv.second - iv.first; }
-                    std::sort(edges.begin(), edges.end());
-                    float uni = 0, both = 0, last = 0;
-                    int depth = 0;
-                    for (auto& e : edges) {
-                        if (depth >= 1) uni += e.first - last;
-                        if (depth >= 2) both += e.first - last;
-                        last = e.first;
-                        depth += e.second;
-                    }
-                    g_prof_overlap[0] = sum0; g_prof_overlap[1] = sum1; g_prof_overlap[2] = uni; g_prof_overlap[3] = both;
-                }
-                (void)hipEventDestroy(ev);
-                if (rc0 < 0) return rc0;
-                if (rc1 < 0) return rc1;
-                return std::max(rc0, rc1);
-            }
-        }
-        if (refused) {
-            const int rcu = svd_batched_one(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes,
-                                            info_host, stream);
-            g_last_path |= ASVD_PATH_SPLIT_REFUSED;
-            return rcu;
-        }
-    }
-    return svd_batched_one(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
-                           stream);
-}
-
-int asvd_svd_batched(int batch, const void* const* a_host, int a_dtype, int64_t m, int64_t n, int64_t lda,
-                     const void* const* cs_host, int cs_dtype, float* const* U_host, float* const* S_host,
-                     float* const* V_host, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes,
-                     int* info_host, void* stream) {
-    try {   // the host driver allocates (std::vector): nothing may be thrown across the C boundary
-        return svd_batched_entry(batch, a_host, a_dtype, m, n, lda, cs_host, cs_dtype, U_host, S_host, V_host, k, max_sweeps, tol, work, work_bytes, info_host,
-                                 stream);
-    } catch (...) {
-        return ASVD_E_HIP;
-    }
-}
-
-int asvd_svd(const void* a, int a_dtype, int64_t m, int64_t n, int64_t lda, const void* col_scale, int cs_dtype, float* U,
-             float* S, float* V, int64_t k, int max_sweeps, float tol, void* work, size_t work_bytes, int* info_host,
-             void* stream) {
-    const void* ap[1] = {a};
-    const void* cp[1] = {col_scale};
-    float* up[1] = {U};
-    float* sp[1] = {S};
-    float* vp[1] = {V};
-    return asvd_svd_batched(1, ap, a_dtype, m, n, lda, col_scale ? cp : nullptr, cs_dtype, (U ? up : nullptr), sp,
-                            (V ? vp : nullptr), k, max_sweeps, tol, work, work_bytes, info_host, stream);
 }
 
 }  // extern "C"
