@@ -27,6 +27,20 @@ def build_model(args):
     return model, tokenizer
 
 
+def run_weight_quant(model, args):
+    """--weight_quant (asvd.py:49-58 of the reference), after the search and the factor gather.  Under --dist with --gather_factors rank0 only
+    rank 0 holds the complete model; the other ranks stop before evaluation, so only rank 0 quantizes.  The result is per row, so it does not
+    depend on which rank computes it."""
+    if args.weight_quant.startswith("awq"):
+        raise NotImplementedError(f"--weight_quant {args.weight_quant} needs the `awq` package (AutoAWQ), which this build does not provide; "
+                                  "use rtn_int8 or rtn_int6")
+    bits = {"rtn_int8": 8, "rtn_int6": 6}[args.weight_quant]
+    if args.dist and args.gather_factors == "rank0" and int(os.environ.get("RANK", "0")) != 0:
+        return
+    from asvd4llm_amd.quantization import rtn_quant_sequential
+    rtn_quant_sequential(model, bits)
+
+
 def main(args):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
@@ -64,7 +78,7 @@ def main(args):
         binary_search_truncation_rank(model, sensitivity, calib_loader, args)
 
         if args.weight_quant != "none":
-            raise NotImplementedError("weight quantization (rtn/awq) is outside the hot-path scope of this build (SURVEY.md §2)")
+            run_weight_quant(model, args)
 
         if args.save_repo and (not args.dist or int(os.environ.get("RANK", "0")) == 0):
             # exported-repo layout of huggingface_repos/build_asvd_repo.py:58-92 (truncation_ranks + ALinear/BLinear keys)

@@ -388,6 +388,51 @@ def reconstruct_err(W, A, B):
     return out
 
 
+def rtn_quant_batched(ws, bits, want_params=False):
+    """Round-to-nearest fake quantization (quantization.py:17-21,31-145 with perchannel=True, sym=False, mse=False) of a list of 2-D
+    device tensors of any shapes, strides (unit column stride) and dtypes, ONE launch per 16 of them (asvd_rtn_quant_batched), then one
+    host sync for the per-tensor flags.  Returns one entry per tensor: the quantized tensor (new, contiguous, same dtype) — or the input
+    tensor itself when one of its rows has scale 0, which the reference leaves unchanged (Quantizer.ready()).  want_params: the entry is
+    (out, q, scale, zero, flagged) with q the uint8 codes [rows, cols] (0 where q is NaN) and scale / zero fp32 [rows]."""
+    lib = L.load(True)
+    if not 1 <= int(bits) <= 8:
+        raise ValueError(f"bits must be in 1..8 (got {bits})")
+    ws = list(ws)
+    if not ws:
+        return []
+    dev = _dev(ws[0], "w").device
+    for w in ws:
+        _dev(w, "w")
+        if w.dim() != 2 or w.stride(1) != 1 or w.device != dev:
+            raise ValueError(f"rtn_quant needs 2-D tensors with unit column stride on one device (got {tuple(w.shape)}, stride {w.stride()}, {w.device})")
+        _dt(w)
+    B = len(ws)
+    outs = [torch.empty(w.shape, dtype=w.dtype, device=dev) for w in ws]
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    if want_params:
+        qs = [torch.empty(w.shape, dtype=torch.uint8, device=dev) for w in ws]
+        scales = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in ws]
+        zeros = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in ws]
+    vp, i64 = ctypes.c_void_p * B, ctypes.c_int64 * B
+    ptrs = lambda ts: vp(*[t.data_ptr() for t in ts])  # noqa: E731
+    with _on(dev):
+        L.check(lib.asvd_rtn_quant_batched(B, ptrs(ws), (ctypes.c_int * B)(*[_dt(w) for w in ws]), i64(*[w.shape[0] for w in ws]),
+                                           i64(*[w.shape[1] for w in ws]), i64(*[w.stride(0) for w in ws]), int(bits), ptrs(outs),
+                                           i64(*[w.shape[1] for w in ws]), ptrs(scales) if want_params else None,
+                                           ptrs(zeros) if want_params else None, ptrs(qs) if want_params else None, _ptr(flags),
+                                           _stream(ws[0])), "asvd_rtn_quant_batched")
+    flagged = [bool(f) for f in flags.tolist()]
+    res = [w if f else o for w, o, f in zip(ws, outs, flagged)]
+    if want_params:
+        return [(o, q, s, z, f) for o, q, s, z, f in zip(res, qs, scales, zeros, flagged)]
+    return res
+
+
+def rtn_quant(w, bits, want_params=False):
+    """rtn_quant_batched for one tensor"""
+    return rtn_quant_batched([w], bits, want_params)[0]
+
+
 PROFILE_CLASSES = ["pack", "sgram", "evd", "supdate", "finalize", "snapshot", "gram1", "update1", "supgram"]
 
 

@@ -1,0 +1,64 @@
+"""RTN weight quantization of the compressed model (quantization.py:147-175 of the reference) on the HIP kernel of csrc/rtn_quant.hip.
+
+The reference's `rtn_quant_sequential(model, wbits)` walks the decoder blocks and, for every module whose type is exactly nn.Linear
+(`find_layers`, which recurses into SVDLinear, so ALinear and BLinear are both quantized), replaces `weight.data` by the per-row
+round-to-nearest fake quantization of the weight, in the weight's own dtype.  lm_head and the embeddings sit outside the blocks and
+are left alone.  Here the weights of one block go through ONE batched launch (ops.rtn_quant_batched); the arithmetic is the
+reference's bit for bit.  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
+import torch
+import torch.nn as nn
+
+from . import ops
+from .modules.svd_linear import SVDLinear
+from .sweep_eval import find_decoder_blocks
+
+
+def _find_linears(module, name=""):
+    """(name, module) of every module of exact type nn.Linear under `module`, in the reference's find_layers order (:147-153)"""
+    if type(module) is nn.Linear:
+        return [(name, module)]
+    res = []
+    for child_name, child in module.named_children():
+        res += _find_linears(child, name + "." + child_name if name != "" else child_name)
+    return res
+
+
+def rtn_targets(model):
+    """(full name, nn.Linear) pairs rtn_quant_sequential quantizes.  The decoder blocks are found by structure
+    (sweep_eval.find_decoder_blocks), not by the model name as the reference does, so families other than llama / opt work too."""
+    blocks_name, blocks = find_decoder_blocks(model)
+    if blocks is None:
+        raise ValueError("no decoder blocks (nn.ModuleList of Linear-holding modules) found in the model")
+    out = []
+    for i, block in enumerate(blocks):
+        out += [(f"{blocks_name}.{i}.{n}", m) for n, m in _find_linears(block)]
+    return out
+
+
+@torch.no_grad()
+def rtn_quant_sequential(model, wbits):
+    """quantization.py:157-175: round-to-nearest `wbits`-bit fake quantization (per output row, asymmetric, no MSE search) of every
+    nn.Linear weight in the decoder blocks, one batched launch per block.  A tensor with a row whose scale is 0 is left unchanged, as
+    the reference's Quantizer.ready() check does.  The one-launch forward copies of every SVDLinear in a block are dropped
+    (refresh_fused), so that they are rebuilt from the quantized factors.  Returns the number of weights replaced."""
+    blocks_name, blocks = find_decoder_blocks(model)
+    if blocks is None:
+        raise ValueError("no decoder blocks (nn.ModuleList of Linear-holding modules) found in the model")
+    dev = getattr(model, "device", None)
+    n_done = 0
+    for block in blocks:
+        if dev is not None:
+            block.to(dev)  # quantization.py:165 `layers[i].to(model.device)`
+        subset = _find_linears(block)
+        if not subset:
+            continue
+        outs = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits)
+        for (_, lin), out in zip(subset, outs):
+            if out is not lin.weight.data:
+                n_done += 1
+            lin.weight.data = out
+        for m in block.modules():
+            if isinstance(m, SVDLinear):
+                m.refresh_fused()
+    print(f"rtn int{wbits}: {n_done} weights quantized in {len(blocks)} blocks of {blocks_name}")
+    return n_done

@@ -255,6 +255,30 @@ int asvd_lowrank_forward_f16(const void* x, int64_t T, const void* Bp, const voi
                              int64_t rp, void* y, void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K11  round-to-nearest weight quantization (fake quantization: the weight keeps its dtype).  Replaces quantization.py:17-21,31-145
+ * (Quantizer.configure(bits, perchannel=True, sym=False, mse=False); find_params(W.float(), weight=True); quantize) as
+ * rtn_quant_sequential (:157-175) applies it to every nn.Linear of the decoder blocks.  Per row of W, in fp32:
+ *   xmin = min(min(row), 0)   xmax = max(max(row), 0)   (both 0: -1 and +1)   maxq = 2^bits - 1
+ *   scale = (xmax - xmin) / maxq    zero = round(-xmin / scale)    q = clamp(round(x / scale) + zero, 0, maxq)
+ *   out = scale * (q - zero), rounded once (RNE) to the weight dtype.
+ * Bit for bit the reference's torch sequence: IEEE fp32 division, round half to even, fp32 denormals kept, NaN-propagating min / max /
+ * clamp (a row holding a NaN or an Inf comes out all NaN, as in torch).  One read and one write of W per row.
+ *   W [rows, cols] in dtype (F32 / F16 / BF16), leading dimension ldw;  out [rows, cols] in the same dtype, ldo; out may be W itself.
+ *   bits in 1..8.  scale, zero: device float[rows] or NULL;  codes: device uint8 [rows, cols] contiguous (q) or NULL (NaN q -> 0).
+ *   flag: device int, caller-zeroed, OR-ed with 1 when some row's scale is 0 (fp32 rows whose values are all of denormal size): the
+ *         reference then returns the tensor UNCHANGED (Quantizer.ready()), so the caller must keep W and discard out.  Such rows are
+ *         copied to out unchanged, the others are quantized, so with out == W a flagged tensor is partly quantized: pass a separate out
+ *         when W may hold such rows.  Asynchronous.
+ * Batched form: one launch per 16 tensors of mixed shapes, strides and dtypes; host arrays [batch] (w_host, dtype_host, rows_host,
+ * cols_host, ldw_host, out_host, ldo_host; scale_host / zero_host / codes_host may be NULL or hold NULL entries); flags: device
+ * int[batch], caller-zeroed, one per tensor. */
+int asvd_rtn_quant(const void* w, int dtype, int64_t rows, int64_t cols, int64_t ldw, int bits, void* out, int64_t ldo, float* scale,
+                   float* zero, void* codes, int* flag, void* stream);
+int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
+                           const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
+                           float* const* zero_host, void* const* codes_host, int* flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

@@ -1,0 +1,149 @@
+"""Benchmark of the RTN weight-quantization step (--weight_quant rtn_int8 / rtn_int6; csrc/rtn_quant.hip) on the decoder Linears of a
+Llama-2-7B-shaped model: the 32 blocks of the dense model (q/k/v/o 4096x4096, gate/up 11008x4096, down 4096x11008, fp16), and the same
+model after ASVD at param ratio 0.9 with rank_align 128 (every Linear an SVDLinear at that ratio: ALinear [out, r] and BLinear [r, in] —
+a uniform stand-in for the searched plan, which depends on calibration data).  Prints ONE JSON line.
+
+Per shape set: kernel time (device events around the 32 per-block batched launches, no host sync in between; median of --iters),
+algorithmic bytes (one read + one write of every weight: 2 x elements x 2 B), GB/s and the fraction of the 8 TB/s HBM spec over kernel time,
+the same step through asvd4llm_amd.quantization's per-block path (with its flag read-back), and the reference's torch sequence
+(quantization.py:17-21,31-145 restated op for op in torch: .float(), row min / max, scale, zero, round, clamp, dequantize, cast back) timed
+on the same GPU, with every output compared bit for bit."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import types
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from asvd4llm_amd import _lib as L  # noqa: E402
+from asvd4llm_amd import ops  # noqa: E402
+from asvd4llm_amd.modules.svd_linear import SVDLinear  # noqa: E402
+
+HBM_SPEC = 8.0e12
+HIDDEN, INTER, BLOCKS = 4096, 11008, 32
+BLOCK_LINEARS = [(HIDDEN, HIDDEN)] * 4 + [(INTER, HIDDEN)] * 2 + [(HIDDEN, INTER)]   # [out, in]
+
+
+def shape_sets(ratio=0.9, align=128):
+    dense = [list(BLOCK_LINEARS) for _ in range(BLOCKS)]
+    asvd = []
+    for _ in range(BLOCKS):
+        blk = []
+        for out_f, in_f in BLOCK_LINEARS:
+            lin = types.SimpleNamespace(weight=types.SimpleNamespace(numel=lambda o=out_f, i=in_f: o * i), in_features=in_f, out_features=out_f)
+            r = SVDLinear.compute_rank(lin, ratio, align)
+            blk += [(out_f, r), (r, in_f)]
+        asvd.append(blk)
+    return {"llama2_7b_dense": dense, f"llama2_7b_asvd{ratio}_align{align}": asvd}
+
+
+@torch.no_grad()
+def torch_sequence(w, bits):
+    """the reference's per-tensor torch ops on the device (find_params + quantize + cast back)"""
+    x = w.float()
+    tmp = torch.zeros(x.shape[0], device=x.device)
+    xmin = torch.minimum(x.min(1)[0], tmp)
+    xmax = torch.maximum(x.max(1)[0], tmp)
+    t = (xmin == 0) & (xmax == 0)
+    xmin[t] = -1
+    xmax[t] = +1
+    maxq = torch.tensor(2 ** bits - 1, device=x.device)
+    scale = ((xmax - xmin) / maxq).reshape(-1, 1)
+    zero = torch.round(-xmin.reshape(-1, 1) / scale)
+    if not torch.all(scale != 0):
+        return w
+    q = torch.clamp(torch.round(x / scale) + zero, 0, maxq)
+    return (scale * (q - zero)).to(w.dtype)
+
+
+def bits_equal(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+def median(xs):
+    s = sorted(xs)
+    return s[len(s) // 2]
+
+
+def run_set(blocks, bits, iters, warmup, dev, seed):
+    lib = L.load(True)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    ws = [[(torch.randn(m, n, generator=g, device=dev, dtype=torch.float32) * 0.02).half() for m, n in blk] for blk in blocks]
+    outs = [[torch.empty_like(w) for w in blk] for blk in ws]
+    flags = torch.zeros(BLOCKS * 16, dtype=torch.int32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    calls = []
+    for b, (blk, oblk) in enumerate(zip(ws, outs)):   # ABI argument arrays built once: the timed window holds launches only
+        n = len(blk)
+        vp, i64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+        calls.append((n, vp(*[w.data_ptr() for w in blk]), (ctypes.c_int * n)(*[L.F16] * n), i64(*[w.shape[0] for w in blk]),
+                      i64(*[w.shape[1] for w in blk]), i64(*[w.stride(0) for w in blk]), bits, vp(*[o.data_ptr() for o in oblk]),
+                      i64(*[o.stride(0) for o in oblk]), None, None, None, ctypes.c_void_p(flags.data_ptr() + 4 * 16 * b), stream))
+
+    def launch_all():
+        for c in calls:
+            L.check(lib.asvd_rtn_quant_batched(*c), "asvd_rtn_quant_batched")
+
+    def timed(fn, n):
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return ts
+
+    timed(launch_all, warmup)
+    kern = timed(launch_all, iters)
+    assert int(flags.sum().item()) == 0
+
+    def ops_path():
+        for blk in ws:
+            ops.rtn_quant_batched(blk, bits)
+    timed(ops_path, max(1, warmup // 2))
+    ops_ms = timed(ops_path, iters)
+
+    def ref_path():
+        return [[torch_sequence(w, bits) for w in blk] for blk in ws]
+    timed(ref_path, 1)
+    ref_ms = timed(ref_path, max(1, iters // 2))
+
+    mismatched, compared = 0, 0
+    for blk, oblk in zip(ws, outs):
+        for w, o in zip(blk, oblk):
+            compared += 1
+            mismatched += not bits_equal(o, torch_sequence(w, bits))
+    elems = sum(w.numel() for blk in ws for w in blk)
+    nbytes = 2 * elems * 2
+    k = median(kern)
+    return {"tensors": sum(len(b) for b in ws), "launches": sum((n + 15) // 16 for n, *_ in calls), "elements": elems, "bytes": nbytes,
+            "kernel_ms": round(k, 4), "kernel_ms_all": [round(t, 4) for t in kern], "gbps": round(nbytes / (k * 1e-3) / 1e9, 1),
+            "frac_of_hbm_spec": round(nbytes / (k * 1e-3) / HBM_SPEC, 4), "ops_path_ms": round(median(ops_ms), 4),
+            "torch_sequence_ms": round(median(ref_ms), 4), "speedup_vs_torch": round(median(ref_ms) / k, 2),
+            "bit_exact_vs_torch": mismatched == 0, "tensors_compared": compared, "tensors_mismatched": mismatched}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bits", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=233)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    L.load(require_device=True)
+    res = {"metric": "rtn_quant_kernel", "bits": args.bits, "dtype": "float16", "hbm_spec_Bps": HBM_SPEC, "sets": {}}
+    for name, blocks in shape_sets().items():
+        res["sets"][name] = run_set(blocks, args.bits, args.iters, args.warmup, dev, args.seed)
+        torch.cuda.empty_cache()
+    res["bit_exact_vs_torch"] = all(s["bit_exact_vs_torch"] for s in res["sets"].values())
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
