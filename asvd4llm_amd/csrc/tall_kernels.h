@@ -63,7 +63,7 @@ __global__ void chol_diag_kernel(const double* __restrict__ G, int64_t ldg, int6
     const int j = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (j >= n_pad) return;
     const double g = G[(int64_t)b * g_batch_stride + (int64_t)j * ldg + j];
-    d[(int64_t)b * n_pad + j] = g > 0.0 ? sqrt(g) : 0.0;
+    d[(int64_t)b * n_pad + j] = g > 0.0 ? sqrt(g) : (g == g ? 0.0 : g);   // a NaN column keeps a NaN norm: it is not a zero column
 }
 
 __global__ void d_to_float_kernel(const double* __restrict__ d, int n, float* __restrict__ df) {
@@ -80,7 +80,7 @@ __global__ void g_permute_scale_kernel(const double* __restrict__ G, int64_t ldg
     if (i == 0) dp[(int64_t)b * n_pad + j] = dj;
     const int lo = pi < pj ? pi : pj, hi = pi < pj ? pj : pi;
     double v;
-    if (i == j) v = 1.0;
+    if (i == j) v = di == di ? 1.0 : di;   // NaN pivot for a NaN column: the Cholesky breaks down and the call reports ASVD_N_NAN
     else v = (di > 0.0 && dj > 0.0) ? G[(int64_t)b * g_batch_stride + (int64_t)lo * ldg + hi] / (di * dj) : 0.0;
     Gs[(int64_t)b * g_batch_stride + (int64_t)i * ldg + j] = v;
 }

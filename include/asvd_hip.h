@@ -126,11 +126,19 @@ int asvd_scale_cols(const void* w, int w_dtype, int64_t m, int64_t n, int64_t ld
  *   U_host      host array [batch] of device pointers to U_b [m, k] row-major (NULL: no vectors)
  *   S_host      host array [batch] of device pointers to S_b [k] descending
  *   V_host      host array [batch] of device pointers to V_b [n, k] row-major (NULL: no vectors)
- *   k           number of leading singular triplets to write, 1 <= k <= min(m, n).  Convergence (tol) is enforced for these
- *               k leading triplets and their orthogonality against the rest; with k < min(m,n) the sweeps stop as soon as
- *               the leading part is done (the discarded tail converges last and would cost 2-4 more sweeps)
- *   max_sweeps  <=0: default (30);  tol <=0: default (1e-6) on max |cos(a_i, a_j)|
- *   info_host   optional host int[4*batch]: {status, sweeps, rotated pairs in last sweep, float bits of the last sweep's max |cos|}
+ *   k           number of leading singular triplets to write, 1 <= k <= min(m, n).  The stopping rule (tol) looks only at the
+ *               kb = min(ceil(k / 32) + 1, panels) leading 32-column panels (those holding the k leading columns plus one panel of
+ *               margin): with k < min(m,n) the sweeps stop as soon as that part is done (the discarded tail converges last and would
+ *               cost 2-4 more sweeps).  The finalisation still ranks ALL columns by norm and writes the k largest.  What a call with
+ *               k < min(m, n) guarantees (tests/test_gpu_svd_topk.py): the contract of a full call on its k triplets — sigma within
+ *               1e-4 of the exact spectrum, orthonormal vectors, and at every rank r <= k a rank-r reconstruction whose error is the
+ *               optimal (Eckart-Young) one to 1e-3 |A diag(s)|_F — no more sweeps than the full call, and the leading k values and
+ *               every rank-r slice equal to the full call's to 2e-6 sigma_1 / 1e-4 relative
+ *   max_sweeps  <=0: default (30)
+ *   tol         <=0: default (1e-6).  Bound on the stopping measure: max |g_ij| / max(g_ii, g_jj) over the column pairs (i, j) that
+ *               touch one of the kb leading panels (g = X^T X of the working columns).  The cosine |g_ij| / sqrt(g_ii g_jj) only
+ *               decides which pairs rotate and which pairs the snapshots of the sparse sweeps mark
+ *   info_host   optional host int[4*batch]: {status, sweeps, rotated pairs in last sweep, float bits of the last sweep's stopping measure}
  * Host-synchronous: the call returns when S/U/V are complete.  Sync points (csrc/svd_jacobi.hip): one after the reduction
  * (Cholesky breakdown flag), one per Jacobi sweep (convergence flags: four ints per problem), one more per sparse sweep
  * (the pair marks of the coupling snapshot go to the host, which packs them into rounds of disjoint pairs), one when a

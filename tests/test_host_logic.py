@@ -253,3 +253,15 @@ def test_decomposition_follows_the_sweep_owner_map_only_while_the_factor_caches_
     assert _decompose_owner_map(model, info, args, 2, True) == flops_map                       # stale: the model was swept with another alpha
     model._asvd_sweep_owner_meta = {"factors_kept": True, "alpha": 0.5, "scaling_method": "abs_mean", "world_size": 4}
     assert _decompose_owner_map(model, info, args, 2, True) == flops_map                       # stale: another world size
+
+
+def test_sweep_rank_hint_is_the_rank_of_the_largest_candidate_ratio():
+    """the k every factorisation of the sweep asks for (tests/test_gpu_svd_topk.py takes it from here): the largest candidate rank, which is the
+    oracle's rank at the largest candidate ratio, aligned or not"""
+    from oracle import asvd_oracle as O
+    from tests.test_gpu_svd_topk import sweep_ranks
+    for m, n in ((1024, 1024), (2048, 2048), (4096, 4096), (11008, 4096), (4096, 11008), (5120, 5120), (13824, 5120), (32000, 4096)):
+        for align in (1, 128):
+            k, R = sweep_ranks(m, n, align)
+            assert k == max(R) == O.rank_from_ratio(m, n, 0.9, align) and len(R) >= 3
+    assert sweep_ranks(4096, 4096)[0] == 1843 and sweep_ranks(4096, 11008)[0] == 2686 and sweep_ranks(4096, 4096, 128)[0] == 1920
