@@ -48,6 +48,9 @@ SIGNATURES = {
     "asvd_rtn_quant": (_i, [_vp, _i, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "asvd_rtn_quant_batched": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64), _i,
                                     _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp]),
+    "asvd_w8_linear_max_tokens": (_i64, []),
+    "asvd_w8_linear_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_w8_dequant": (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i64, _vp]),
     "asvd_fro_worksize": (_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

@@ -9,6 +9,11 @@ are loaded (huggingface_repos/modeling_asvd_llama.py:5-41).  `save_asvd_repo` wr
 it emits are generated from the templates below (subclassing the stock HF config/model classes), so the directory loads
 with `AutoModelForCausalLM.from_pretrained(path, trust_remote_code=True)` as the published `hahnyuan/*-asvd*` repos do.
 `load_asvd_repo` is a family-agnostic loader that needs no remote code; it also reads repos exported by the reference.
+
+A model whose weights were packed (`--weight_quant_storage packed`: W8Linear modules) is written as it is — the checkpoint then holds
+`<layer>.qweight` (uint8), `.scales`, `.zeros` (fp32) in place of `<layer>.weight` — with `"weight_quant": {"method": "rtn", "bits": b,
+"storage": "uint8"}` in config.json and WITHOUT `auto_map` and the remote-code files, which cannot rebuild packed modules: such a repo loads
+with `load_asvd_repo` only.
 """
 import json
 import os
@@ -17,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from .modules.svd_linear import SVDLinear
+from .modules.w8_linear import W8Linear
 
 _FAMILIES = {
     # family tag -> (HF config class, HF model class, file stem)
@@ -99,8 +105,29 @@ def replace_with_factor_pairs(model, truncation_ranks, dtype=None):
     return model
 
 
+def packed_layers_of(model):
+    """{full layer name: bits} of every W8Linear, in named_modules order"""
+    return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, W8Linear)}
+
+
+def replace_with_packed(model, state, bits=8, dtype=None):
+    """Swap every module whose checkpoint keys end in `.qweight` for an empty W8Linear of the checkpoint's shape, so that the packed keys fit."""
+    for key in [k for k in state if k.endswith(".qweight")]:
+        full_name = key[: -len(".qweight")]
+        parent_name, _, child = full_name.rpartition(".")
+        parent = model.get_submodule(parent_name) if parent_name else model
+        old = getattr(parent, child)
+        out_f, in_f = state[key].shape
+        if not isinstance(old, nn.Linear) or (old.out_features, old.in_features) != (out_f, in_f):
+            raise ValueError(f"{full_name}: packed weight {tuple(state[key].shape)} does not fit {old}")
+        setattr(parent, child, W8Linear(in_f, out_f, bias=old.bias is not None, bits=bits, weight_dtype=dtype or old.weight.dtype,
+                                        device=old.weight.device))
+    return model
+
+
 def save_asvd_repo(model, save_path, tokenizer=None, family=None):
-    """Write `save_path/` in the reference's exported-repo layout.  Returns the truncation_ranks dict."""
+    """Write `save_path/` in the reference's exported-repo layout.  Returns the truncation_ranks dict.  A model with packed weights
+    (W8Linear) gets `weight_quant` in config.json and no remote-code loader (see the module docstring)."""
     fam = family or _family_of(model)
     cls_config, cls_model, stem = _FAMILIES[fam]
     Fam = {"llama": "Llama", "opt": "OPT"}[fam]
@@ -111,6 +138,16 @@ def save_asvd_repo(model, save_path, tokenizer=None, family=None):
     config = model.config.to_dict()
     ranks = truncation_ranks_of(model)
     config["truncation_ranks"] = ranks
+    packed = packed_layers_of(model)
+    if packed:
+        if len(set(packed.values())) != 1:
+            raise ValueError(f"packed layers of several bit widths in one model: {sorted(set(packed.values()))}")
+        config["weight_quant"] = {"method": "rtn", "bits": next(iter(packed.values())), "storage": "uint8"}
+        config.pop("auto_map", None)
+        with open(os.path.join(save_path, "config.json"), "w") as f:
+            json.dump(config, f, indent=2)
+        print(f"{len(packed)} packed (uint8) weights: no auto_map / remote-code files written, load with asvd4llm_amd.export.load_asvd_repo")
+        return ranks
     config["auto_map"] = {
         "AutoConfig": f"configuration_asvd_{stem}.ASVD{Fam}Config",
         "AutoModelForCausalLM": f"modeling_asvd_{stem}.ASVD{Fam}ForCausalLM",
@@ -163,6 +200,14 @@ def load_asvd_repo(path, dtype=torch.float16, device="cpu"):
         torch.set_default_dtype(prev)
     replace_with_factor_pairs(model, ranks, dtype=dtype)
     state = _read_state_dict(path)
+    wq = raw.get("weight_quant") or {}
+    if any(k.endswith(".qweight") for k in state):
+        # the codes stand for weights of ONE dtype, the model's at pack time (save_pretrained records it); loading them as another would
+        # round every weight once more and take the packed layers off the kernel path
+        packed_dtype = raw.get("torch_dtype") or raw.get("dtype")
+        if packed_dtype is not None and getattr(torch, str(packed_dtype), None) != dtype:
+            raise ValueError(f"{path} holds weights packed from {packed_dtype}; load it with dtype=torch.{packed_dtype} (got {dtype})")
+        replace_with_packed(model, state, bits=int(wq.get("bits", 8)), dtype=dtype)
     missing, unexpected = model.load_state_dict(state, strict=False)
     tied_ok = {"lm_head.weight"} if getattr(cfg, "tie_word_embeddings", False) else set()
     bad_missing = [k for k in missing if k not in tied_ok and not k.endswith("rotary_emb.inv_freq")]

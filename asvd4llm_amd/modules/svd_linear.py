@@ -354,9 +354,11 @@ class SVDLinear(nn.Module):
         # profiles/r5_k10_nostrict.jsonl; under ASVD_STRICT the wrapper used to read the give-up flag after every launch: +18 us, now every 64th).  Everywhere
         # else the reference's two GEMMs through nn.Linear: at par from 64 tokens on and on the 11008-wide MLP projections (DESIGN.md
         # section 4 has the table).  Opt-in (ASVD_FUSED_FORWARD=1 / self.fused_forward): see _fused_forward_enabled.
-        if ((getattr(self, "fused_forward", False) or _fused_forward_enabled()) and inp.is_cuda and inp.dtype == torch.float16 and self.BLinear.weight.dtype == torch.float16 and inp.shape[-1] % 64 == 0
-                and 0 < inp.numel() // inp.shape[-1] <= FUSED_FORWARD_MAX_TOKENS and max(self.ALinear.out_features, inp.shape[-1]) <= FUSED_FORWARD_MAX_OUT
+        # (the plain-nn.Linear test comes before anything reads `.weight`: packed factors, modules/w8_linear.py, have none and fall through)
+        if ((getattr(self, "fused_forward", False) or _fused_forward_enabled()) and inp.is_cuda and inp.dtype == torch.float16
                 and _plain_linear_without_hooks(self.ALinear) and _plain_linear_without_hooks(self.BLinear) and self.BLinear.bias is None
+                and self.BLinear.weight.dtype == torch.float16 and inp.shape[-1] % 64 == 0
+                and 0 < inp.numel() // inp.shape[-1] <= FUSED_FORWARD_MAX_TOKENS and max(self.ALinear.out_features, inp.shape[-1]) <= FUSED_FORWARD_MAX_OUT
                 and not (torch.is_grad_enabled() and (inp.requires_grad or self.ALinear.weight.requires_grad or self.BLinear.weight.requires_grad))):
             Ap, Bp, work = self._fused_state(torch.cuda.current_stream(inp.device).cuda_stream)
             x2d = inp.reshape(-1, inp.shape[-1])

@@ -1,0 +1,92 @@
+"""W8Linear — a Linear whose RTN-quantized weight stays packed: uint8 codes plus one fp32 scale and zero per output row.
+
+The weight it stands for is  w[n, k] = (scales[n] * (qweight[n, k] - zeros[n])).to(weight_dtype),  the value the fake quantizer
+(quantization.rtn_quant_sequential) writes into an nn.Linear, bit for bit.  Decode-sized fp16 inputs run on the W8A16 kernel of
+csrc/w8_linear.hip, which dequantizes to exactly that value in registers; every other input dequantizes the layer's weight into a temporary
+(csrc/w8_linear.hip as well) and calls F.linear on it, so the model's resident size stays packed.
+
+Not an nn.Linear subclass on purpose: collect_linear_info, the calibration hooks and quantization._find_linears select nn.Linear modules and
+must keep ignoring packed ones."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+
+# Token count up to which forward() takes the kernel: the measured crossover (tools/bench_w8_forward.py --force_kernel --tokens 1,4,16,32,64 on
+# MI355X, profiles/w8_forward.json).  Against the fake-quantized fp16 weights through nn.Linear on the Llama-2-7B ASVD-0.9
+# shape set with rank_align 128 the packed pass takes 0.72 / 0.73 / 0.86 of the time at 1 / 4 / 16 tokens in device time (graph replay; 0.69 / 0.70 /
+# 0.76 eager) and 1.07 / 1.28 at 32 / 64 (the kernel re-reads x once per workgroup, which costs more than the halved weight stream saves from 32
+# tokens on).  These figures hold for rows that allow 16-byte loads only: see W8Linear.kernel_rows_ok.
+W8_FORWARD_MAX_TOKENS = 16
+
+
+class W8Linear(nn.Module):
+    """y = x w^T + bias with w held as `qweight` uint8 [out, in], `scales` fp32 [out], `zeros` fp32 [out] (persistent buffers: they are what
+    state_dict() and save_pretrained() write) and an optional `bias` buffer in the original dtype."""
+
+    def __init__(self, in_features, out_features, bias=True, bits=8, weight_dtype=torch.float16, device=None):
+        super().__init__()
+        if not 1 <= int(bits) <= 8:
+            raise ValueError(f"bits must be in 1..8 (got {bits}): one code per byte")
+        self.in_features, self.out_features, self.bits, self.weight_dtype = int(in_features), int(out_features), int(bits), weight_dtype
+        self.register_buffer("qweight", torch.zeros((self.out_features, self.in_features), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.zeros(self.out_features, dtype=torch.float32, device=device))
+        self.register_buffer("zeros", torch.zeros(self.out_features, dtype=torch.float32, device=device))
+        self.register_buffer("bias", torch.zeros(self.out_features, dtype=weight_dtype, device=device) if bias else None)
+
+    @classmethod
+    def from_codes(cls, qweight, scales, zeros, bias, bits, weight_dtype):
+        """wrap the outputs of ops.rtn_quant_batched(..., want_params=True) without copying them"""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.out_features, self.in_features = (int(d) for d in qweight.shape)
+        self.bits, self.weight_dtype = int(bits), weight_dtype
+        self.register_buffer("qweight", qweight)
+        self.register_buffer("scales", scales)
+        self.register_buffer("zeros", zeros)
+        self.register_buffer("bias", bias)
+        return self
+
+    def _apply(self, fn, *args, **kwargs):
+        # The buffers DEFINE the weight: a dtype cast of the model (.half(), .double(), .to(dtype)) must not touch the fp32 scales and zeros,
+        # and the bias stays in weight_dtype with the weight it belongs to.  Device moves go through.  forward() casts to the input's dtype.
+        keep = {n: getattr(self, n) for n in ("scales", "zeros", "bias") if getattr(self, n) is not None}
+        super()._apply(fn, *args, **kwargs)
+        for n, old in keep.items():
+            new = getattr(self, n)
+            if new.dtype != old.dtype:
+                setattr(self, n, old.to(new.device))
+        return self
+
+    def dequantize(self):
+        """the weight in weight_dtype.  CUDA: csrc/w8_linear.hip; CPU: the same arithmetic in torch (fp32 subtraction, one fp32 product, one
+        rounding)"""
+        if self.qweight.is_cuda:
+            return ops.w8_dequant(self.qweight, self.scales, self.zeros, self.weight_dtype)
+        return (self.scales[:, None] * (self.qweight.float() - self.zeros[:, None])).to(self.weight_dtype)
+
+    def kernel_rows_ok(self):
+        """the code rows allow the kernel's 16-byte loads: in_features % 16 == 0 and 16-byte-aligned contiguous storage.  Other rows (odd ranks:
+        K = 1843) would run the kernel on element loads, measured 2-4x SLOWER than fp16 nn.Linear (profiles/w8_forward_align1.json): forward()
+        keeps them off the kernel"""
+        q = self.qweight
+        return self.in_features % 16 == 0 and q.is_contiguous() and q.data_ptr() % 16 == 0
+
+    def forward(self, x):
+        tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        if (x.is_cuda and x.dtype == torch.float16 and self.weight_dtype == torch.float16 and 0 < tokens <= W8_FORWARD_MAX_TOKENS
+                and (self.bias is None or self.bias.dtype == torch.float16) and not (torch.is_grad_enabled() and x.requires_grad)
+                and self.kernel_rows_ok()):
+            x2d = x.reshape(-1, x.shape[-1])
+            x2d = x2d if x2d.is_contiguous() else x2d.contiguous()
+            if x2d.data_ptr() % 16 == 0:
+                y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias)
+                return y.view(*x.shape[:-1], self.out_features)
+        w, b = self.dequantize(), self.bias
+        if x.dtype != w.dtype:   # a model cast to another dtype: the same weight, converted for the GEMM (exact into a wider type)
+            w, b = w.to(x.dtype), None if b is None else b.to(x.dtype)
+        return F.linear(x, w, b)
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, bits={self.bits}, weight_dtype={self.weight_dtype}"

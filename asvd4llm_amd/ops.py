@@ -433,6 +433,55 @@ def rtn_quant(w, bits, want_params=False):
     return rtn_quant_batched([w], bits, want_params)[0]
 
 
+W8_MAX_TOKENS = 256  # ASVD_W8_MAX_TOKENS (asvd_w8_linear_max_tokens)
+
+
+def w8_linear(x2d, q, scale, zero, bias=None):
+    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (q - zero)) dequantized in registers (K12, asvd_w8_linear_f16): x2d [T <= 256, K] fp16
+    contiguous, q [N, K] uint8 (unit column stride), scale / zero [N] fp32, bias [N] fp16 or None.  One launch, deterministic."""
+    lib = L.load(True)
+    _dev(x2d, "x")
+    if x2d.dim() != 2 or q.dim() != 2 or x2d.dtype != torch.float16 or q.dtype != torch.uint8 or not x2d.is_contiguous() or q.stride(1) != 1:
+        raise ValueError(f"w8_linear needs x [T, K] fp16 contiguous and q [N, K] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, {tuple(q.shape)} {q.dtype})")
+    T, K = x2d.shape
+    N = q.shape[0]
+    if q.shape[1] != K or not 1 <= T <= W8_MAX_TOKENS:
+        raise ValueError(f"w8_linear: x {tuple(x2d.shape)} against q {tuple(q.shape)}; 1 <= tokens <= {W8_MAX_TOKENS}")
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != N or zero.numel() != N or not scale.is_contiguous() \
+            or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
+        raise ValueError("w8_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
+    if q.device != x2d.device or scale.device != x2d.device or zero.device != x2d.device or (bias is not None and bias.device != x2d.device):
+        raise ValueError("w8_linear: all tensors must live on the device of x")
+    y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
+    with _on(x2d.device):
+        L.check(lib.asvd_w8_linear_f16(x2d.data_ptr(), T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(),
+                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_w8_linear_f16")
+    return y
+
+
+def w8_dequant(q, scale, zero, dtype, out=None):
+    """the dense weight scale * (q - zero) in `dtype` (fp16 / bf16 / fp32), value for value the `out` of rtn_quant for these codes
+    (asvd_w8_dequant).  q [rows, cols] uint8 with unit column stride; out: optional destination [rows, cols] with unit column stride."""
+    lib = L.load(True)
+    _dev(q, "q")
+    if q.dim() != 2 or q.dtype != torch.uint8 or q.stride(1) != 1 or dtype not in _DT:
+        raise ValueError(f"w8_dequant needs q [rows, cols] uint8 with unit column stride and a float dtype (got {tuple(q.shape)} {q.dtype}, {dtype})")
+    rows, cols = q.shape
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
+            or not zero.is_contiguous() or scale.device != q.device or zero.device != q.device:
+        raise ValueError("w8_dequant needs scale / zero [rows] fp32 contiguous on the device of q")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != dtype or out.stride(1) != 1 or out.device != q.device:
+        raise ValueError(f"w8_dequant: out must be [{rows}, {cols}] {dtype} with unit column stride on the device of q")
+    if rows == 0 or cols == 0:
+        return out
+    with _on(q.device):
+        L.check(lib.asvd_w8_dequant(q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), rows, cols, out.data_ptr(), _DT[dtype],
+                                    out.stride(0), _stream(q)), "asvd_w8_dequant")
+    return out
+
+
 PROFILE_CLASSES = ["pack", "sgram", "evd", "supdate", "finalize", "snapshot", "gram1", "update1", "supgram"]
 
 

@@ -4,12 +4,13 @@ The reference's `rtn_quant_sequential(model, wbits)` walks the decoder blocks an
 (`find_layers`, which recurses into SVDLinear, so ALinear and BLinear are both quantized), replaces `weight.data` by the per-row
 round-to-nearest fake quantization of the weight, in the weight's own dtype.  lm_head and the embeddings sit outside the blocks and
 are left alone.  Here the weights of one block go through ONE batched launch (ops.rtn_quant_batched); the arithmetic is the
-reference's bit for bit.  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
+reference's bit for bit.  `rtn_pack_sequential` is the same step with the weights kept as uint8 codes (modules/w8_linear.py).  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from .modules.svd_linear import SVDLinear
+from .modules.w8_linear import W8Linear
 from .sweep_eval import find_decoder_blocks
 
 
@@ -62,3 +63,54 @@ def rtn_quant_sequential(model, wbits):
                 m.refresh_fused()
     print(f"rtn int{wbits}: {n_done} weights quantized in {len(blocks)} blocks of {blocks_name}")
     return n_done
+
+
+def _set_submodule(root, name, new):
+    parent_name, _, child = name.rpartition(".")
+    setattr(root.get_submodule(parent_name) if parent_name else root, child, new)
+
+
+@torch.no_grad()
+def rtn_pack_sequential(model, wbits):
+    """rtn_quant_sequential with the result kept PACKED: per decoder block one batched launch that also emits the uint8 codes and the per-row
+    fp32 scale / zero, and every target nn.Linear replaced by a W8Linear holding them (one byte per weight for any wbits <= 8; the bias is
+    kept as it is).  The packed layer stands for exactly the fake-quantized weight: W8Linear.dequantize() is the `out` of the launch, bit
+    for bit.  That is checked on the device for every tensor before it is replaced; a tensor stays an nn.Linear — fake-quantized, or
+    unchanged when the kernel flags a row with scale 0, exactly as rtn_quant_sequential leaves it — when its fake-quantized weight holds a
+    non-finite value or its codes do not reproduce it (one flag read-back per block).  Returns the number of weights packed."""
+    blocks_name, blocks = find_decoder_blocks(model)
+    if blocks is None:
+        raise ValueError("no decoder blocks (nn.ModuleList of Linear-holding modules) found in the model")
+    dev = getattr(model, "device", None)
+    n_packed, bytes_before, bytes_after = 0, 0, 0
+    for block in blocks:
+        if dev is not None:
+            block.to(dev)
+        subset = _find_linears(block)
+        if not subset:
+            continue
+        res = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, want_params=True)
+        bad = []
+        for (_, lin), (out, q, scale, zero, flagged) in zip(subset, res):
+            if flagged:
+                bad.append(torch.ones((), dtype=torch.bool, device=q.device))
+            else:
+                back = ops.w8_dequant(q, scale, zero, out.dtype)
+                bits_t = torch.int32 if out.dtype == torch.float32 else torch.int16
+                bad.append(~torch.isfinite(out).all() | (back.view(bits_t) != out.view(bits_t)).any())
+        bad = torch.stack(bad).tolist()   # the one read-back of the block
+        for (name, lin), (out, q, scale, zero, flagged), keep in zip(subset, res, bad):
+            nbytes = lin.weight.numel() * lin.weight.element_size()
+            if keep:
+                lin.weight.data = out   # the input itself when flagged (ops.rtn_quant_batched)
+                continue
+            bias = lin.bias.data if lin.bias is not None else None
+            _set_submodule(block, name, W8Linear.from_codes(q, scale, zero, bias, wbits, out.dtype))
+            n_packed += 1
+            bytes_before += nbytes
+            bytes_after += q.numel() + 4 * (scale.numel() + zero.numel())
+        for m in block.modules():
+            if isinstance(m, SVDLinear):
+                m.refresh_fused()
+    print(f"rtn int{wbits} packed: {n_packed} weights in {len(blocks)} blocks, {bytes_before} -> {bytes_after} bytes")
+    return n_packed

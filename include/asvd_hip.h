@@ -287,6 +287,27 @@ int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtyp
                            float* const* zero_host, void* const* codes_host, int* flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K12  RTN-quantized weights kept as uint8 codes (the q / scale / zero of K11): forward and dequantization.
+ *   w[n, k] = scale[n] * (float(q[n, k]) - zero[n]), evaluated in fp32 (the subtraction is exact) and rounded once (RNE) to the weight dtype:
+ *   bit for bit the `out` of asvd_rtn_quant for the same codes.
+ * asvd_w8_linear_f16:  y[T, N] = fp16( x[T, K] . w^T + bias ) with w dequantized to fp16 in registers, fp32 accumulation on the fp16 matrix
+ *   pipe and one rounding at the end: nn.Linear on the fake-quantized weight up to the order of the fp32 sums.  One launch; the k range is split
+ *   over the waves of a workgroup and summed in a fixed order (no atomics, nothing crosses workgroups): two calls give identical bits.
+ *   x [T, K] fp16 contiguous, 1 <= T <= ASVD_W8_MAX_TOKENS (asvd_w8_linear_max_tokens() returns it);  q [N, ldq] uint8, ldq >= K;  scale, zero
+ *   [N] fp32;  bias [N] fp16 or NULL;  y [T, N] fp16 contiguous;  any K >= 1, any N >= 1.  Rows are streamed with 16-byte loads when x and q are
+ *   16-byte aligned, K % 8 == 0 and ldq % 16 == 0 (element loads for the last K % 16 codes, and throughout otherwise).  The element-load form is correct but slow (measured 3.3-3.7x the time
+ *   of an fp16 GEMM at K = 1843): callers that care about speed send such layers through asvd_w8_dequant + their GEMM.  x, y and bias must be 2-byte aligned.
+ *   An SVDLinear with packed factors is two calls (z, then y).  Asynchronous.
+ * asvd_w8_dequant:  out [rows, cols] (ldo) in out_dtype (F32 / F16 / BF16) from q [rows, ldq], scale, zero [rows].  Asynchronous.
+ * Bad arguments (NULL, T out of range, ldq < K, misaligned x / y / out) return ASVD_E_BADARG before any device call. */
+#define ASVD_W8_MAX_TOKENS 256
+int64_t asvd_w8_linear_max_tokens(void);
+int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias,
+                       int64_t N, int64_t K, void* y, void* stream);
+int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out, int out_dtype,
+                    int64_t ldo, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

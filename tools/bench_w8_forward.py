@@ -1,0 +1,154 @@
+"""Benchmark of the packed (uint8 codes, W8A16 kernel: csrc/w8_linear.hip) forward against the fake-quantized fp16 weights through nn.Linear,
+on the decoder Linears of a Llama-2-7B-shaped model: the dense model and the model after ASVD at param ratio 0.9 with rank_align 128 (the
+shape sets of tools/bench_rtn.py).  Prints ONE JSON line.  Needs a gfx950 device; there is no fallback.
+
+One pass walks the Linears of all 32 blocks, every block with its OWN weights (fp16 set ~13 / ~11 GB, packed set ~6.5 / ~6 GB: far beyond the
+256 MiB Infinity Cache, so a pass streams from HBM; a loop over one layer would time the cache).  An SVDLinear is BLinear then ALinear, the
+intermediate feeding the second.  Per token count (--tokens, default 1, 4, 16, 64):
+  (a) nn.Linear modules holding the fake-quantized fp16 weights (what --weight_quant rtn_int8 leaves today),
+  (b) W8Linear modules holding the codes of the same quantization (--weight_quant_storage packed),
+alternating, device events around each pass, median / min / max / spread (max - min) of --iters passes after --warmup.  At these sizes an eager
+pass is bound by the host (Python and launch cost per layer, for both paths), so every figure is reported twice: "eager" as a user's forward runs,
+and "graph" with one pass of each path captured into a device graph and replayed (no host work inside the timed window: what the device does).  (b) also gets its
+algorithmic bytes (codes + 8 bytes per row + activations in and out), GB/s and the share of the 8 TB/s HBM spec, and the largest difference
+between the outputs of (a) and (b) over all layers, relative to the largest output."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asvd4llm_amd import _lib as L  # noqa: E402
+from asvd4llm_amd import ops  # noqa: E402
+from asvd4llm_amd.modules import w8_linear as W  # noqa: E402
+from bench_rtn import HBM_SPEC, median, shape_sets  # noqa: E402
+
+TOKENS = (1, 4, 16, 64)
+
+
+def build_set(blocks, factored, bits, dev, seed):
+    """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear) stages applied in order (BLinear, ALinear for a factored
+    layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    out = []
+    for blk in blocks:
+        ws = [(torch.randn(m, n, generator=g, device=dev, dtype=torch.float32) * 0.02).half() for m, n in blk]
+        res = ops.rtn_quant_batched(ws, bits, want_params=True)
+        stages = []
+        for fake, q, scale, zero, flagged in res:
+            assert not flagged
+            lin = nn.Linear(fake.shape[1], fake.shape[0], bias=False, device="meta")
+            lin.weight = nn.Parameter(fake, requires_grad=False)
+            stages.append((lin, W.W8Linear.from_codes(q, scale, zero, None, bits, torch.float16)))
+        out.append([[stages[i + 1], stages[i]] for i in range(0, len(stages), 2)] if factored else [[s] for s in stages])
+    return out
+
+
+@torch.no_grad()
+def run_pass(layers, xs, which):
+    for blk in layers:
+        for layer in blk:
+            y = xs[layer[0][0].in_features]
+            for stage in layer:
+                y = stage[which](y)
+    return y
+
+
+def timed_pair(layers, xs, iters, warmup, graph):
+    ta, tb = [], []
+    if graph:   # one pass of each path, captured once (a linear chain of launches) and replayed
+        run = []
+        for which in (0, 1):
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                run_pass(layers, xs, which)
+            run.append(gr.replay)
+    else:
+        run = [lambda: run_pass(layers, xs, 0), lambda: run_pass(layers, xs, 1)]
+    for it in range(warmup + iters):
+        for which, ts in ((0, ta), (1, tb)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run[which]()
+            e1.record()
+            e1.synchronize()
+            if it >= warmup:
+                ts.append(e0.elapsed_time(e1))
+    return ta, tb
+
+
+@torch.no_grad()
+def max_difference(layers, xs):
+    worst, top = 0.0, 0.0
+    for blk in layers:
+        for layer in blk:
+            ya = yb = xs[layer[0][0].in_features]
+            for lin, packed in layer:
+                ya, yb = lin(ya), packed(yb)
+            worst = max(worst, (ya.float() - yb.float()).abs().max().item())
+            top = max(top, ya.float().abs().max().item())
+    return worst, top
+
+
+def stats(ts):
+    return {"median_ms": round(median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "spread_ms": round(max(ts) - min(ts), 4),
+            "all_ms": [round(t, 4) for t in ts]}
+
+
+def run_set(blocks, factored, args, dev):
+    layers = build_set(blocks, factored, args.bits, dev, args.seed)
+    stages = [s for blk in layers for layer in blk for s in layer]
+    code_bytes = sum(p.qweight.numel() + 8 * p.out_features for _, p in stages)
+    fp16_bytes = sum(2 * lin.weight.numel() for lin, _ in stages)
+    res = {"launches_per_pass": len(stages), "fp16_weight_bytes": fp16_bytes, "packed_weight_bytes": code_bytes, "tokens": {}}
+    g = torch.Generator(device=dev).manual_seed(args.seed + 1)
+    for T in args.tokens:
+        xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
+        act_bytes = sum(2 * T * (lin.in_features + lin.out_features) for lin, _ in stages)
+        nbytes = code_bytes + act_bytes
+        diff, top = max_difference(layers, xs)
+        rec = {"kernel_dispatched": T <= W.W8_FORWARD_MAX_TOKENS, "packed_bytes": nbytes, "max_abs_diff": diff, "max_abs_output": top,
+               "max_rel_diff": diff / top if top else 0.0}
+        for mode in ("eager", "graph"):
+            ta, tb = timed_pair(layers, xs, args.iters, args.warmup, mode == "graph")
+            a, b = stats(ta), stats(tb)
+            rec[mode] = {"fp16_linear": a, "packed": b, "packed_over_fp16": round(b["median_ms"] / a["median_ms"], 4),
+                         "packed_not_slower": b["median_ms"] <= a["median_ms"] + a["spread_ms"],
+                         "packed_gbps": round(nbytes / (b["median_ms"] * 1e-3) / 1e9, 1),
+                         "packed_frac_of_hbm_spec": round(nbytes / (b["median_ms"] * 1e-3) / HBM_SPEC, 4),
+                         "fp16_gbps": round((fp16_bytes + act_bytes) / (a["median_ms"] * 1e-3) / 1e9, 1)}
+        res["tokens"][str(T)] = rec
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--bits", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=233)
+    ap.add_argument("--tokens", type=lambda v: [int(t) for t in v.split(",")], default=list(TOKENS), help="token counts, comma separated")
+    ap.add_argument("--rank_align", type=int, default=128, help="rank alignment of the ASVD shape set (1: ranks such as 1843, whose rows allow no 16-byte loads)")
+    ap.add_argument("--force_kernel", action="store_true", help="measure the kernel at every token count and for every row alignment, whatever W8Linear.forward dispatches")
+    args = ap.parse_args()
+    if args.iters < 10:
+        ap.error("--iters must be at least 10")
+    L.load(require_device=True)
+    dev = torch.device("cuda", 0)
+    if args.force_kernel:
+        W.W8_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
+        W.W8Linear.kernel_rows_ok = lambda self: True   # rows that allow no 16-byte loads too (--rank_align 1)
+    res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
+           "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
+    for name, blocks in shape_sets(0.9, args.rank_align).items():
+        res["sets"][name] = run_set(blocks, "asvd" in name, args, dev)
+        torch.cuda.empty_cache()
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
