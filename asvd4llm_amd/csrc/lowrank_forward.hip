@@ -21,6 +21,11 @@
 //
 // Layout contract (the Python module pads once at construction):  Bp [rp, K] = B with zero rows appended, Ap [N, rp] = A with zero
 // columns appended, rp a multiple of 64, K a multiple of 64.
+//
+// Non-finite activations: a token row of y depends on its own row of x only, so a NaN / Inf in one row leaves every other row bit-identical.
+// The row itself is non-finite wherever the two-Linear reference is, but not necessarily of the same class: an Inf in x is multiplied by the
+// zero rows of Bp (padded ranks, rp > r) and, in the GEMV kernel, by the zeros a masked lane holds in place of weights beyond the row
+// (gemv_rows), and Inf * 0 = NaN reaches z and from there every y of the row.  The row was lost already; no other row is touched.
 #include "common.h"
 
 namespace {

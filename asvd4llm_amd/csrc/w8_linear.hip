@@ -18,6 +18,9 @@
 // an output element depends on its own two rows only, and those elements are not stored.  What K leaves beyond a multiple of 128 goes in
 // 16-code chunks (16-byte loads while a chunk is whole, element loads for the last one, zero beyond K); rows that are not 16-byte aligned
 // take element loads throughout.
+//
+// Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
+// with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
 #include "common.h"
 #include <atomic>
 
