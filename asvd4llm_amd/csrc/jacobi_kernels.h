@@ -263,6 +263,47 @@ __global__ __launch_bounds__(256) void panel_sumsq_kernel(Sched sc, const float*
 
 __device__ __forceinline__ float nanmax(float a, float b) { return (b != b) ? b : ((a != a) ? a : fmaxf(a, b)); }
 
+// The mark step of a snapshot, for the 32 x 32 block (panel I, panel J), I <= J, that a wave holds as a 32x32 MFMA accumulator: lane (c = lane & 31,
+// h = lane >> 5) has g[i][c], i = (reg & 3) + 8 (reg >> 2) + 4 h, from g_of(reg, i).  Cosine |g| / sqrt(d_i d_j) against tol marks the pair (I, J);
+// |g| / max(d_i, d_j) of the blocks that touch the first kb panels goes into the termination maximum; a NaN anywhere makes the maximum NaN.
+template <class GOf>
+__device__ __forceinline__ void snapshot_mark(int I, int J, int lane, const float* __restrict__ dnb, float dj, float tol, int kb, int nb, int b,
+                                              unsigned char* __restrict__ pflag, unsigned* __restrict__ maxoff_bits, GOf g_of) {
+    const int h = lane >> 5, c = lane & 31;
+    float v = 0.0f, vt = 0.0f;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int i = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        if (I == J && i == c) continue;
+        const float di = dnb[I * PB + i];
+        const float g = g_of(reg, i, di);
+        const float dd = di * dj;
+        float x = (dd > 0.0f) ? fabsf(g) * rsqrtf(dd) : 0.0f;
+        if (g != g || dd != dd) x = __builtin_nanf("");
+        const float mx = fmaxf(di, dj);
+        float xt = (mx > 0.0f) ? fabsf(g) / mx : 0.0f;
+        if (x != x) xt = x;
+        v = nanmax(v, x);
+        vt = nanmax(vt, xt);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        v = nanmax(v, __shfl_xor(v, o, 64));
+        vt = nanmax(vt, __shfl_xor(vt, o, 64));
+    }
+    if (lane == 0) {
+        if (v != v) {
+            atomicMax(&maxoff_bits[b], 0x7fc00000u);
+        } else {
+            if (v >= tol) {  // a coupling inside a panel is repaired by any visit of that panel: mark its neighbour pair
+                const int A = (I == J) ? min(I, I ^ 1) : I, Bp = (I == J) ? max(I, I ^ 1) : J;
+                pflag[((int64_t)b * nb + A) * nb + Bp] = 1;
+            }
+            if (I < kb || J < kb) atomicMax(&maxoff_bits[b], __float_as_uint(vt));
+        }
+    }
+}
+
 // grid (ceil(nb/4), ceil(nb/4), batch); upper-triangular tiles only.  Wave w owns panel J = 4*jg + w against panels I = 4*ig + a.
 // 32-row chunks of the eight panels are staged in LDS (coalesced 16-B loads, next chunk prefetched into registers while the
 // current one is in the matrix pipe); every wave reads its operands from LDS as conflict-free 256-B rows.
@@ -359,45 +400,13 @@ __global__ __launch_bounds__(256) void fullcheck_kernel(Sched sc, const float* _
         }
     }
     if (J >= nb) return;
-    const int h = lane >> 5, c = lane & 31;
-    const float dj = dnb[J * PB + c];
+    const float dj = dnb[J * PB + (lane & 31)];
     const int ej = col_exp(dj);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         if (!ok[a]) continue;
-        const int I = ig * 4 + a;
-        float v = 0.0f, vt = 0.0f;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int i = (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            if (I == J && i == c) continue;
-            const float di = dnb[I * PB + i];
-            const float g = ldexpf(acc[a][reg], col_exp(di) + ej);   // back to the scale of the data
-            const float dd = di * dj;
-            float x = (dd > 0.0f) ? fabsf(g) * rsqrtf(dd) : 0.0f;
-            if (g != g || dd != dd) x = __builtin_nanf("");
-            const float mx = fmaxf(di, dj);
-            float xt = (mx > 0.0f) ? fabsf(g) / mx : 0.0f;
-            if (x != x) xt = x;
-            v = nanmax(v, x);
-            vt = nanmax(vt, xt);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            v = nanmax(v, __shfl_xor(v, o, 64));
-            vt = nanmax(vt, __shfl_xor(vt, o, 64));
-        }
-        if (lane == 0) {
-            if (v != v) {
-                atomicMax(&maxoff_bits[b], 0x7fc00000u);
-            } else {
-                if (v >= tol) {  // a coupling inside a panel is repaired by any visit of that panel: mark its neighbour pair
-                    const int A = (I == J) ? min(I, I ^ 1) : I, Bp = (I == J) ? max(I, I ^ 1) : J;
-                    pflag[((int64_t)b * nb + A) * nb + Bp] = 1;
-                }
-                if (I < kb || J < kb) atomicMax(&maxoff_bits[b], __float_as_uint(vt));
-            }
-        }
+        snapshot_mark(ig * 4 + a, J, lane, dnb, dj, tol, kb, nb, b, pflag, maxoff_bits,
+                      [&](int reg, int, float di) { return ldexpf(acc[a][reg], col_exp(di) + ej); });  // back to the scale of the data
     }
 }
 

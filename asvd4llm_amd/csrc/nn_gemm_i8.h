@@ -1,5 +1,5 @@
 // nn_gemm_i8.h — the long-side product Y = X Vr of the tall path's epilogue on the int8 matrix pipe (included by svd_jacobi.hip inside its anonymous
-// namespace, after gram_i8.h).  Round 6.
+// namespace, after i8_digits.h and gram_i8.h).  Round 6.
 //
 // nn_gemm_split_kernel (tall_kernels.h) forms every fp32 product from six bf16 products with fp32 accumulation and splits its operands inside the GEMM
 // loop.  Here both operands become 24-bit fixed-point numbers ONCE, outside the loop, and the products are integer:
@@ -24,24 +24,6 @@ __global__ void colexp_from_norm_kernel(const double* __restrict__ d, int n, int
     if (!(v == v) || v > 1.7e308) e = GI_BAD;
     else if (v > 0.0) { (void)frexp(v, &e); }  // v = f 2^e, f in [0.5, 1)
     bex[i] = e;
-}
-
-// Maxima of |x| 2^shift over a row / column are taken on KEYS (exponent + shift in the high bits, mantissa below: ordered like the scaled magnitudes,
-// with no intermediate overflow or underflow); 0 = all zero, 0xffffffff = Inf / NaN met.
-__device__ __forceinline__ unsigned gi_key(float x, int shift) {
-    const unsigned a = __float_as_uint(x) & 0x7fffffffu;
-    if (a >= 0x7f800000u) return 0xffffffffu;
-    if (a == 0u) return 0u;
-    int e;
-    const float f = frexpf(__uint_as_float(a), &e);                 // f in [0.5, 1)
-    const unsigned mant = (unsigned)ldexpf(f, 24) - 0x800000u;      // 23 bits, exact
-    const int ee = min(max(e + shift + 256, 1), 510);                // nine bits; beyond 2^+-254 of the scale the order no longer matters
-    return ((unsigned)ee << 23) | mant;
-}
-__device__ __forceinline__ int gi_exp_of_key(unsigned key) {       // E with (max) 2^-E < 127/128
-    if (key == 0xffffffffu) return GI_BAD;
-    if (key == 0u) return GI_ZERO;
-    return (int)(key >> 23) - 256 + ((key & 0x7fffffu) >= 0x7e0000u ? 1 : 0);
 }
 
 // aex[z][r] = alpha_r.  grid (ceil(rows / 8), zb), 256 threads: eight rows x 32 lanes over the columns of a panel.
@@ -89,20 +71,10 @@ __global__ __launch_bounds__(256) void split_xt_i8_kernel(const float* __restric
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             // a row that holds Inf / NaN (ae == GI_BAD): digits of no meaning, the epilogue writes NaN for the row
-            const int t = (ae == GI_BAD || be[i] == GI_ZERO || be[i] == GI_BAD) ? 0 : (int)rintf(ldexpf(x[i], 23 - be[i] - ae));
-            const int d2 = (int)(signed char)(t & 0xff);
-            const int t1 = (t - d2) >> 8;
-            const int d1 = (int)(signed char)(t1 & 0xff);
-            const int d0 = (t1 - d1) >> 8;
-            w0[i >> 2] |= (unsigned)(d0 & 0xff) << (8 * (i & 3));
-            w1[i >> 2] |= (unsigned)(d1 & 0xff) << (8 * (i & 3));
-            w2[i >> 2] |= (unsigned)(d2 & 0xff) << (8 * (i & 3));
+            gi_pack_digits((ae == GI_BAD || be[i] == GI_ZERO || be[i] == GI_BAD) ? 0 : (int)rintf(ldexpf(x[i], 23 - be[i] - ae)), i, w0, w1, w2);
         }
     }
-    signed char* pb = planes + (int64_t)z * 3 * plane_stride + (((int64_t)RP * cgs + cg) * 32 + rr) * 16;
-    *(uint4*)(pb) = make_uint4(w0[0], w0[1], w0[2], w0[3]);
-    *(uint4*)(pb + plane_stride) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
-    *(uint4*)(pb + 2 * plane_stride) = make_uint4(w2[0], w2[1], w2[2], w2[3]);
+    gi_store_digits(planes + (int64_t)z * 3 * plane_stride + (((int64_t)RP * cgs + cg) * 32 + rr) * 16, plane_stride, w0, w1, w2);
 }
 
 // vmax[z][j] = key of max_c |v[c][j]| 2^beta_c  (pre-zeroed; grid (ceil(k / 256), row chunks, zb), atomic max)
@@ -141,24 +113,14 @@ __global__ __launch_bounds__(256) void split_v_i8_kernel(TallBatch tb, int cols,
                 const int be = bex[(int64_t)z * n_pad + c];
                 if (be != GI_ZERO && be != GI_BAD) t = (int)rintf(ldexpf(V[(int64_t)c * ldv + j], 23 + be - ge));
             }
-            const int d2 = (int)(signed char)(t & 0xff);
-            const int t1 = (t - d2) >> 8;
-            const int d1 = (int)(signed char)(t1 & 0xff);
-            const int d0 = (t1 - d1) >> 8;
-            w0[i >> 2] |= (unsigned)(d0 & 0xff) << (8 * (i & 3));
-            w1[i >> 2] |= (unsigned)(d1 & 0xff) << (8 * (i & 3));
-            w2[i >> 2] |= (unsigned)(d2 & 0xff) << (8 * (i & 3));
+            gi_pack_digits(t, i, w0, w1, w2);
         }
     }
-    signed char* pb = planes + (int64_t)z * 3 * plane_stride + (((int64_t)JP * cgs + cg) * 32 + jj) * 16;
-    *(uint4*)(pb) = make_uint4(w0[0], w0[1], w0[2], w0[3]);
-    *(uint4*)(pb + plane_stride) = make_uint4(w1[0], w1[1], w1[2], w1[3]);
-    *(uint4*)(pb + 2 * plane_stride) = make_uint4(w2[0], w2[1], w2[2], w2[3]);
+    gi_store_digits(planes + (int64_t)z * 3 * plane_stride + (((int64_t)JP * cgs + cg) * 32 + jj) * 16, plane_stride, w0, w1, w2);
 }
 
-// out[z][r0 + ..][..] = Y.  Workgroup = 512 threads = one 128 (rows) x 128 (columns) block on the tiling of gram_i8_kernel: wave w owns row panels
-// 4 Ib + 2 (w >> 2) + {0, 1} against column panel 4 Jb + (w & 3) — 2 tiles x 4 weights x 16 = 128 accumulators, two waves per SIMD; stages of 64 reduction
-// indices through LDS in the planes' own order.  grid: (column blocks x row blocks of this segment, zb); the blocks go in 4 x 8 groups per XCD where the
+// out[z][r0 + ..][..] = Y.  Workgroup = 512 threads = one 128 (rows) x 128 (columns) block: gi_tile_loop (i8_digits.h) with four weights, the planes of
+// X^T on the A side and those of Vr on the B side.  grid: (column blocks x row blocks of this segment, zb); the blocks go in 4 x 8 groups per XCD where the
 // grid allows it, plainly otherwise (row runs per XCD were measured too, no difference: tools/bench_i8_gemm.py, round 6; removed).
 // (First version, measured: four waves of 64 x 64 with SIX products, weight <= 2 — 17 ms per 32 x 4096^2, but on rows with a spike over a floor 1e-3
 // below it the floor's values sit in the low digits and the dropped weight-3 products were 2.4e-5 of sigma_1 in U sigma, fifty times the bf16 form.)
@@ -183,83 +145,19 @@ __global__ __launch_bounds__(512) void nn_gemm_i8_kernel(TallBatch tb, const sig
             Jb = id % gx;
         }
     }
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wi = w >> 2, wj = w & 3;
-    const unsigned char* gsrc[6];
-    bool gok[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const int q = r * 512 + tid;
-        const int side = q / 1536, qq = q % 1536;
-        const int a = (qq >> 7) >> 2, p4 = (qq >> 7) & 3, within = qq & 127;
-        if (side == 0) {
-            const int P = 4 * Ib + p4;
-            gok[r] = P < rps;
-            gsrc[r] = (const unsigned char*)planesA + (int64_t)z * 3 * strideA + (int64_t)a * strideA + (int64_t)(gok[r] ? P : 0) * cgs * 512 + within * 16;
-        } else {
-            const int P = 4 * Jb + p4;
-            gok[r] = P < jps;
-            gsrc[r] = (const unsigned char*)planesB + (int64_t)z * 3 * strideB + (int64_t)a * strideB + (int64_t)(gok[r] ? P : 0) * cgs * 512 + within * 16;
-        }
-    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wi = w >> 2, wj = w & 3;
     i32x16 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][s][i] = 0;
-    const int nstage = cgs >> 2;  // cgs is a multiple of 4
-    uint4 stg[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) stg[r] = gok[r] ? *(const uint4*)(gsrc[r]) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) *(uint4*)(gi_lds + (r * 512 + tid) * 16) = stg[r];
-    __syncthreads();
-    for (int st = 0; st < nstage; ++st) {
-        const unsigned char* cur = gi_lds + (st & 1) * GI_STAGE_BYTES;
-        if (st + 1 < nstage) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) stg[r] = gok[r] ? *(const uint4*)(gsrc[r] + (int64_t)(st + 1) * 2048) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            i32x4 fa[2][3], fb[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-                    fa[t][a] = *(const i32x4*)(cur + (((0 * 3 + a) * 4 + 2 * wi + t) * 4 + 2 * ks) * 512 + lane * 16);
-                fb[a] = *(const i32x4*)(cur + (((1 * 3 + a) * 4 + wj) * 4 + 2 * ks) * 512 + lane * 16);
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        if (a + c < 4) acc[t][a + c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[t][a], fb[c], acc[t][a + c], 0, 0, 0);
-        }
-        if (st + 1 < nstage) {
-            unsigned char* nxt = gi_lds + ((st + 1) & 1) * GI_STAGE_BYTES;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) *(uint4*)(nxt + (r * 512 + tid) * 16) = stg[r];
-        }
-        __syncthreads();
-    }
-    // D[i][j]: j = lane & 31 (B operand = column panel), i = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (A operand = row panel)
+    gi_tile_loop<4>(planesA + (int64_t)z * 3 * strideA, strideA, rps, planesB + (int64_t)z * 3 * strideB, strideB, jps, Ib, Jb, cgs, gi_lds, acc);
     const int j = (4 * Jb + wj) * 32 + (lane & 31);
     if (j >= k) return;
-    const int ge = gex[(int64_t)z * kp + j];
-    const double sj = ge == GI_BAD ? __builtin_nan("") : (ge == GI_ZERO ? 0.0 : ldexp(1.0, ge - 23));
+    const double sj = gi_scale(gex[(int64_t)z * kp + j]);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int r = r0 + (4 * Ib + 2 * wi + t) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
             if (r >= rows) continue;
-            const int ae = aex[(int64_t)z * rows_pad + r];
-            const double si = ae == GI_BAD ? __builtin_nan("") : (ae == GI_ZERO ? 0.0 : ldexp(1.0, ae - 23));
+            const double si = gi_scale(aex[(int64_t)z * rows_pad + r]);
             double v = (double)acc[t][3][reg] * 256.0;
             v += (double)acc[t][2][reg] * 65536.0;
             v += (double)acc[t][1][reg] * 16777216.0;

@@ -57,6 +57,7 @@ using namespace asvdk;
 
 #include "jacobi_kernels.h"
 #include "tall_kernels.h"
+#include "i8_digits.h"
 #include "gram_i8.h"
 #include "nn_gemm_i8.h"
 #include "snapshot_i8.h"
