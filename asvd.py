@@ -35,9 +35,18 @@ def run_weight_quant(model, args):
         raise NotImplementedError(f"--weight_quant {args.weight_quant} needs the `awq` package (AutoAWQ), which this build does not provide; "
                                   "use rtn_int8 or rtn_int6")
     bits = {"rtn_int8": 8, "rtn_int6": 6}[args.weight_quant]
+    storage = getattr(args, "weight_quant_storage", "fake")
+    if storage == "bitpacked" and bits == 8:
+        raise ValueError("--weight_quant_storage bitpacked with rtn_int8: 8-bit codes are already one per byte: use packed")
     if args.dist and args.gather_factors == "rank0" and int(os.environ.get("RANK", "0")) != 0:
         return
-    if getattr(args, "weight_quant_storage", "fake") == "packed":
+    if storage == "bitpacked":
+        # ... with the codes stored at their own width (WBLinear modules: 6 bits per weight; the same weights and, at decode sizes, the same
+        # output bits as `packed`)
+        from asvd4llm_amd.quantization import rtn_pack_sequential
+        rtn_pack_sequential(model, bits, storage="bits")
+        return
+    if storage == "packed":
         # the same quantization with the weights kept as uint8 codes (W8Linear modules, W8A16 forward kernel at decode sizes)
         from asvd4llm_amd.quantization import rtn_pack_sequential
         rtn_pack_sequential(model, bits)
@@ -128,10 +137,11 @@ def build_parser():
     parser.add_argument("--use_cache", action="store_true", help="use cached calibration results")
     parser.add_argument("--weight_quant", type=str, default="none", choices=["none", "rtn_int8", "rtn_int6", "awq_int8", "awq_int4"],
                         help="weight quantization method")
-    parser.add_argument("--weight_quant_storage", type=str, default="fake", choices=["fake", "packed"],
+    parser.add_argument("--weight_quant_storage", type=str, default="fake", choices=["fake", "packed", "bitpacked"],
                         help="rtn_int8 / rtn_int6: `fake` writes the quantized weights back in their dtype (the reference's behaviour); `packed` keeps "
                              "them as uint8 codes with per-row fp32 scale and zero (one byte per weight, also for int6) and runs decode-sized "
-                             "inputs on the W8A16 kernel; both stand for the same weights bit for bit")
+                             "inputs on the W8A16 kernel; `bitpacked` (rtn_int6 only) stores the codes at 6 bits per weight and runs the kernel that unpacks "
+                             "them in registers; all three stand for the same weights bit for bit")
     parser.add_argument("--eval_mmlu", action="store_true", help="evaluate mmlu")
     parser.add_argument("--eval_ppl", default="wikitext2,ptb", type=str)
     parser.add_argument("--eval_tasks", type=str, default="")

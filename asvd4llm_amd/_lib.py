@@ -51,6 +51,10 @@ SIGNATURES = {
     "asvd_w8_linear_max_tokens": (_i64, []),
     "asvd_w8_linear_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "asvd_w8_dequant": (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i64, _vp]),
+    "asvd_wb_row_bytes": (_i64, [_i64, _i]),
+    "asvd_wb_pack": (_i, [_vp, _i64, _i64, _i64, _i, _vp, _i64, _vp]),
+    "asvd_wb_dequant": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _vp, _i, _i64, _vp]),
+    "asvd_wb_linear_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "asvd_fro_worksize": (_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

@@ -19,6 +19,12 @@
 // 16-code chunks (16-byte loads while a chunk is whole, element loads for the last one, zero beyond K); rows that are not 16-byte aligned
 // take element loads throughout.
 //
+// K13, codes stored at their own width (bits = 6 or 4): a row is a little-endian bitstream, code k in bits [bits k, bits (k + 1)) of the row read
+// as one integer, zero-padded to whole blocks of 64 codes (8 bits bytes: 48 or 32).  Block 2 it + g is exactly what lane (i, g) owns in iteration
+// `it`, so the tile loop is the one above with three or two 16-byte loads per lane and iteration instead of four; the codes are cut out of the
+// loaded words with constant shifts (w8_code) and go through the same subtraction, product and conversion, chunk m to MFMA m, so
+// asvd_wb_linear_f16 gives the bits of asvd_w8_linear_f16 on the same codes.  asvd_wb_pack / asvd_wb_dequant write and read the format.
+//
 // Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
 // with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
 #include "common.h"
@@ -35,10 +41,23 @@ constexpr int W8_KIT = 128;   // k values per iteration of a wave
 constexpr int W8_MAX_DEVICES = 64;   // devices whose CU count the host entry caches
 constexpr int W8_U = 2;       // iterations whose loads a wave issues before the first use
 
+// 32-bit words that hold a chunk of 16 codes of BITS bits, and with it 16-byte words that hold a lane's block of 64
+template <int BITS> constexpr int W8_CW = BITS / 2;
+
+// code j (a constant after unrolling) of the 16 codes in w[]: bits [BITS j, BITS (j + 1)) of the words read as one little-endian integer.  At 8
+// and 4 bits no code crosses a word; at 6 bits codes 5 and 10 do
+template <int BITS>
+__device__ __forceinline__ uint32_t w8_code(const uint32_t (&w)[W8_CW<BITS>], int j) {
+    const int bit = BITS * j, lo = bit >> 5, sh = bit & 31;
+    uint32_t v = w[lo] >> sh;
+    if (sh + BITS > 32) v |= w[lo + 1 < W8_CW<BITS> ? lo + 1 : lo] << ((32 - sh) & 31);
+    return v & ((1u << BITS) - 1u);
+}
+
 // the fp32 value scale * (code - zero).  It must exist as an fp32 value before the cast: the backend otherwise folds product + cast into one
 // v_fma_mixlo_f16 (one rounding instead of the quantizer's two), whatever the contraction setting (rtn_quant.hip does the same)
-__device__ __forceinline__ float w8_value(uint32_t word, int b, float scale, float zero) {
-    float o = scale * ((float)((word >> (8 * b)) & 0xffu) - zero);
+__device__ __forceinline__ float w8_value(uint32_t code, float scale, float zero) {
+    float o = scale * ((float)code - zero);
     asm volatile("" : "+v"(o));
     return o;
 }
@@ -46,28 +65,34 @@ __device__ __forceinline__ float w8_value(uint32_t word, int b, float scale, flo
 typedef float w8_f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 w8_f16x2 __attribute__((ext_vector_type(2)));
 
-// four codes of one 32-bit word -> four fp16 values in two words (one packed conversion per pair); elements at or beyond `valid` (of this
-// word) are zero
-template <bool MASK>
-__device__ __forceinline__ void w8_word_f16(uint32_t word, float scale, float zero, int valid, uint32_t& lo, uint32_t& hi) {
-    w8_f32x2 a, b;
-    a.x = w8_value(word, 0, scale, zero), a.y = w8_value(word, 1, scale, zero);
-    b.x = w8_value(word, 2, scale, zero), b.y = w8_value(word, 3, scale, zero);
-    lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, w8_f16x2));
-    hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(b, w8_f16x2));
-    if (MASK) {
-        lo &= (valid > 0 ? 0xffffu : 0u) | (valid > 1 ? 0xffff0000u : 0u);
-        hi &= (valid > 2 ? 0xffffu : 0u) | (valid > 3 ? 0xffff0000u : 0u);
+// 16 codes -> the two 8-value MFMA operands (one packed conversion per pair of codes); elements at or beyond `valid` are zero
+template <int BITS, bool MASK>
+__device__ __forceinline__ void w8_chunk_f16(const uint32_t (&w)[W8_CW<BITS>], float scale, float zero, int valid, uint4& w0, uint4& w1) {
+    uint32_t h[8];
+#pragma unroll
+    for (int p = 0; p < 8; p += 2) {   // four values, then their two conversions
+        w8_f32x2 a, b;
+        a.x = w8_value(w8_code<BITS>(w, 2 * p), scale, zero), a.y = w8_value(w8_code<BITS>(w, 2 * p + 1), scale, zero);
+        b.x = w8_value(w8_code<BITS>(w, 2 * p + 2), scale, zero), b.y = w8_value(w8_code<BITS>(w, 2 * p + 3), scale, zero);
+        h[p] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, w8_f16x2));
+        h[p + 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(b, w8_f16x2));
+        if (MASK) {
+            h[p] &= (valid > 2 * p ? 0xffffu : 0u) | (valid > 2 * p + 1 ? 0xffff0000u : 0u);
+            h[p + 1] &= (valid > 2 * p + 2 ? 0xffffu : 0u) | (valid > 2 * p + 3 ? 0xffff0000u : 0u);
+        }
     }
+    w0 = make_uint4(h[0], h[1], h[2], h[3]);
+    w1 = make_uint4(h[4], h[5], h[6], h[7]);
 }
 
-// 16 codes -> the two 8-value MFMA operands
-template <bool MASK>
-__device__ __forceinline__ void w8_chunk_f16(const uint4& c, float scale, float zero, int valid, uint4& w0, uint4& w1) {
-    w8_word_f16<MASK>(c.x, scale, zero, valid, w0.x, w0.y);
-    w8_word_f16<MASK>(c.y, scale, zero, valid - 4, w0.z, w0.w);
-    w8_word_f16<MASK>(c.z, scale, zero, valid - 8, w1.x, w1.y);
-    w8_word_f16<MASK>(c.w, scale, zero, valid - 12, w1.z, w1.w);
+// word c (a constant after unrolling) of a 16-byte load
+__device__ __forceinline__ uint32_t w8_word(const uint4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
+// the words of chunk m (16 codes) of a lane's 64-code block, loaded as BITS / 2 16-byte words
+template <int BITS>
+__device__ __forceinline__ void w8_chunk_words(const uint4 (&cv)[W8_CW<BITS>], int m, uint32_t (&w)[W8_CW<BITS>]) {
+#pragma unroll
+    for (int t = 0; t < W8_CW<BITS>; ++t) w[t] = w8_word(cv[(W8_CW<BITS> * m + t) >> 2], (W8_CW<BITS> * m + t) & 3);
 }
 
 // 16 code bytes at p[0..15], the first `valid` of them readable (zero for the others); constant indices only (no scratch)
@@ -92,27 +117,35 @@ __device__ __forceinline__ f32x16 w8_mfma(const uint4& a, const uint4& b, f32x16
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
 }
 
-// one iteration of a lane: its 64 codes and 64 x values (16-byte loads), and the 8 MFMAs that consume them
-__device__ __forceinline__ void w8_iter_load(uint4 (&cv)[4], uint4 (&xv)[8], const uint8_t* __restrict__ qrow, const uint16_t* __restrict__ xr, int it) {
-    const uint4* cp = (const uint4*)(qrow + (int64_t)it * W8_KIT);
+// one iteration of a lane: its 64 codes (8 BITS bytes) and 64 x values (16-byte loads), and the 8 MFMAs that consume them
+template <int BITS>
+__device__ __forceinline__ void w8_iter_load(uint4 (&cv)[W8_CW<BITS>], uint4 (&xv)[8], const uint8_t* __restrict__ qrow, const uint16_t* __restrict__ xr,
+                                             int it) {
+    const uint4* cp = (const uint4*)(qrow + (int64_t)it * (W8_KIT * BITS / 8));
     const uint4* xp = (const uint4*)(xr + (int64_t)it * W8_KIT);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) cv[m] = cp[m];
+    for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cp[m];
 #pragma unroll
     for (int m = 0; m < 8; ++m) xv[m] = xp[m];
 }
 
-__device__ __forceinline__ f32x16 w8_iter_mfma(const uint4 (&cv)[4], const uint4 (&xv)[8], float sc, float zr, f32x16 acc) {
+template <int BITS>
+__device__ __forceinline__ f32x16 w8_iter_mfma(const uint4 (&cv)[W8_CW<BITS>], const uint4 (&xv)[8], float sc, float zr, f32x16 acc) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
+        uint32_t w[W8_CW<BITS>];
         uint4 w0, w1;
-        w8_chunk_f16<false>(cv[m], sc, zr, 16, w0, w1);
+        w8_chunk_words<BITS>(cv, m, w);
+        w8_chunk_f16<BITS, false>(w, sc, zr, 16, w0, w1);
         acc = w8_mfma(xv[2 * m], w0, acc);
         acc = w8_mfma(xv[2 * m + 1], w1, acc);
     }
     return acc;
 }
 
+// BITS = 8: q holds one code per byte, ldq >= K.  BITS = 6, 4: q holds the bitstream rows (ldq bytes apart), K % 16 == 0 and everything is
+// 16-byte aligned (vec is 1)
+template <int BITS>
 __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
                                                               const float* __restrict__ scale, const float* __restrict__ zero,
                                                               const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ft,
@@ -124,7 +157,7 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
     const int nvalid = min(ft, N - n0), tvalid = min(32, T - t0);
     const int wrow = n0 + min(i, nvalid - 1), xrow = t0 + min(i, tvalid - 1);
     const float sc = scale[wrow], zr = zero[wrow];
-    const uint8_t* qrow = q + (int64_t)wrow * ldq + 64 * g;
+    const uint8_t* qrow = q + (int64_t)wrow * ldq + 8 * BITS * g;   // the lane's 64-code block of iteration 0
     const uint16_t* xr = x + (int64_t)xrow * K + 64 * g;
     f32x16 acc;
 #pragma unroll
@@ -134,40 +167,56 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
     // one workgroup per CU a wave hides latency only by loads in flight); the iterations left over go one at a time ----
     int base = wave;
     for (; base + W8_WAVES * (W8_U - 1) < nkfull; base += W8_WAVES * W8_U) {
-        uint4 cv[W8_U][4], xv[W8_U][8];
+        uint4 cv[W8_U][W8_CW<BITS>], xv[W8_U][8];
 #pragma unroll
-        for (int u = 0; u < W8_U; ++u) w8_iter_load(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
+        for (int u = 0; u < W8_U; ++u) w8_iter_load<BITS>(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
 #pragma unroll
-        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma(cv[u], xv[u], sc, zr, acc);
+        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma<BITS>(cv[u], xv[u], sc, zr, acc);
     }
     for (; base < nkfull; base += W8_WAVES) {
-        uint4 cv[4], xv[8];
-        w8_iter_load(cv, xv, qrow, xr, base);
-        acc = w8_iter_mfma(cv, xv, sc, zr, acc);
+        uint4 cv[W8_CW<BITS>], xv[8];
+        w8_iter_load<BITS>(cv, xv, qrow, xr, base);
+        acc = w8_iter_mfma<BITS>(cv, xv, sc, zr, acc);
     }
 
     // ---- what is left (K % 128, or every iteration when the rows are not 16-byte aligned): chunk by chunk, zero beyond K ----
     const int nk = (K + W8_KIT - 1) / W8_KIT;
     // (iteration `it` belongs to wave it % 4 on both paths, so the result does not depend on which path the alignment selects)
     for (int it = nkfull + ((wave - nkfull) & (W8_WAVES - 1)); it < nk; it += W8_WAVES) {
+        uint4 cv[W8_CW<BITS>];
+        if (BITS != 8) {   // the lane's block as a whole (rows are padded to whole blocks); a block that starts at or beyond K is not there
+#pragma unroll
+            for (int m = 0; m < W8_CW<BITS>; ++m)
+                cv[m] = it * W8_KIT + 64 * g < K ? ((const uint4*)(qrow + (int64_t)it * (W8_KIT * BITS / 8)))[m] : make_uint4(0, 0, 0, 0);
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int k0 = it * W8_KIT + 64 * g + 16 * m;       // first k of this lane's chunk
             const int valid = max(0, min(16, K - k0));
-            const uint8_t* cp = qrow + (int64_t)it * W8_KIT + 16 * m;
             const uint16_t* xp = xr + (int64_t)it * W8_KIT + 16 * m;
-            uint4 c, x0, x1;
-            if (vec && valid == 16) {   // a whole chunk of aligned rows (K % 128 >= 16): 16-byte loads here too
-                c = *(const uint4*)cp;
-                x0 = ((const uint4*)xp)[0];
-                x1 = ((const uint4*)xp)[1];
+            uint32_t w[W8_CW<BITS>];
+            uint4 x0, x1;
+            if (BITS != 8) {   // K % 16 == 0: a chunk is whole or absent; the padding codes of an absent one are masked below, x is zero
+                w8_chunk_words<BITS>(cv, m, w);
+                x0 = valid == 16 ? ((const uint4*)xp)[0] : make_uint4(0, 0, 0, 0);
+                x1 = valid == 16 ? ((const uint4*)xp)[1] : make_uint4(0, 0, 0, 0);
             } else {
-                c = w8_load_codes_tail(cp, valid);
-                x0 = w8_load_x_tail(xp, min(8, valid));
-                x1 = w8_load_x_tail(xp + 8, valid - 8);
+                const uint8_t* cp = qrow + (int64_t)it * W8_KIT + 16 * m;
+                uint4 c;
+                if (vec && valid == 16) {   // a whole chunk of aligned rows (K % 128 >= 16): 16-byte loads here too
+                    c = *(const uint4*)cp;
+                    x0 = ((const uint4*)xp)[0];
+                    x1 = ((const uint4*)xp)[1];
+                } else {
+                    c = w8_load_codes_tail(cp, valid);
+                    x0 = w8_load_x_tail(xp, min(8, valid));
+                    x1 = w8_load_x_tail(xp + 8, valid - 8);
+                }
+#pragma unroll
+                for (int t = 0; t < W8_CW<BITS>; ++t) w[t] = w8_word(c, t & 3);
             }
             uint4 w0, w1;
-            w8_chunk_f16<true>(c, sc, zr, valid, w0, w1);
+            w8_chunk_f16<BITS, true>(w, sc, zr, valid, w0, w1);
             acc = w8_mfma(x0, w0, acc);
             acc = w8_mfma(x1, w1, acc);
         }
@@ -208,15 +257,15 @@ __global__ __launch_bounds__(W8_THREADS) void w8_dequant_kernel(const uint8_t* _
         if (DT == ASVD_F32) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                ((uint4*)op)[j] = make_uint4(__float_as_uint(w8_value(w[j], 0, sc, zr)), __float_as_uint(w8_value(w[j], 1, sc, zr)),
-                                             __float_as_uint(w8_value(w[j], 2, sc, zr)), __float_as_uint(w8_value(w[j], 3, sc, zr)));
+                ((uint4*)op)[j] = make_uint4(__float_as_uint(w8_value(w[j] & 0xffu, sc, zr)), __float_as_uint(w8_value((w[j] >> 8) & 0xffu, sc, zr)),
+                                             __float_as_uint(w8_value((w[j] >> 16) & 0xffu, sc, zr)), __float_as_uint(w8_value(w[j] >> 24, sc, zr)));
         } else {
             uint32_t h[8];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const float a = w8_value(w[j], 2 * p, sc, zr), b = w8_value(w[j], 2 * p + 1, sc, zr);
+                    const float a = w8_value((w[j] >> (16 * p)) & 0xffu, sc, zr), b = w8_value((w[j] >> (16 * p + 8)) & 0xffu, sc, zr);
                     h[2 * j + p] = DT == ASVD_F16 ? ((uint32_t)f32_to_f16_bits(a) | ((uint32_t)f32_to_f16_bits(b) << 16))
                                                   : ((uint32_t)f32_to_bf16_bits(a) | ((uint32_t)f32_to_bf16_bits(b) << 16));
                 }
@@ -234,7 +283,100 @@ __global__ __launch_bounds__(W8_THREADS) void w8_dequant_elem_kernel(const uint8
     const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
     if (id >= rows * cols) return;
     const int64_t row = id / cols, c = id - row * cols;
-    elem<DT>::st(out, row * ldo + c, w8_value((uint32_t)q[row * ldq + c], 0, scale[row], zero[row]));
+    elem<DT>::st(out, row * ldo + c, w8_value((uint32_t)q[row * ldq + c], scale[row], zero[row]));
+}
+
+// ---- codes at their own width: pack and dequantization -----------------------------------------------------------------------------
+// bytes of a bitstream row of `cols` codes: whole blocks of 64 codes
+__host__ __device__ inline int64_t wb_row_bytes(int64_t cols, int bits) { return (cols + 63) / 64 * 8 * bits; }
+
+// one thread per 16 consecutive codes of a padded row: BITS / 2 words of the bitstream (4-byte stores).  Codes are masked to BITS bits, codes
+// at or beyond cols are the padding zeros
+template <int BITS>
+__global__ __launch_bounds__(W8_THREADS) void wb_pack_kernel(const uint8_t* __restrict__ q, int64_t ldq, int64_t rows, int64_t cols,
+                                                            uint8_t* __restrict__ out, int64_t ld_bytes) {
+    const int64_t chunks = (cols + 63) / 64 * 4;
+    const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
+    if (id >= rows * chunks) return;
+    const int64_t row = id / chunks, c0 = (id - row * chunks) * 16;
+    const uint8_t* qp = q + row * ldq + c0;
+    uint32_t w[W8_CW<BITS>];
+#pragma unroll
+    for (int t = 0; t < W8_CW<BITS>; ++t) w[t] = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const uint32_t code = c0 + j < cols ? (uint32_t)qp[j] & ((1u << BITS) - 1u) : 0u;
+        const int bit = BITS * j, lo = bit >> 5, sh = bit & 31;
+        w[lo] |= code << sh;
+        if (sh + BITS > 32) w[lo + 1 < W8_CW<BITS> ? lo + 1 : lo] |= code >> ((32 - sh) & 31);
+    }
+    uint32_t* op = (uint32_t*)(out + row * ld_bytes + c0 / 8 * BITS);
+#pragma unroll
+    for (int t = 0; t < W8_CW<BITS>; ++t) op[t] = w[t];
+}
+
+// one thread per 16 consecutive codes of a row (4-byte loads of the bitstream).  vec: whole chunks and an aligned destination, 16-byte stores;
+// otherwise element stores, none at or beyond cols
+template <int DT, int BITS>
+__global__ __launch_bounds__(W8_THREADS) void wb_dequant_kernel(const uint8_t* __restrict__ q, int64_t ld_bytes, const float* __restrict__ scale,
+                                                               const float* __restrict__ zero, int64_t rows, int64_t cols, void* __restrict__ out,
+                                                               int64_t ldo, int vec) {
+    const int64_t chunks = (cols + 15) / 16;
+    const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
+    if (id >= rows * chunks) return;
+    const int64_t row = id / chunks, c0 = (id - row * chunks) * 16;
+    const float sc = scale[row], zr = zero[row];
+    const uint32_t* qp = (const uint32_t*)(q + row * ld_bytes + c0 / 8 * BITS);
+    uint32_t w[W8_CW<BITS>];
+#pragma unroll
+    for (int t = 0; t < W8_CW<BITS>; ++t) w[t] = qp[t];
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = w8_value(w8_code<BITS>(w, j), sc, zr);
+    if (vec) {
+        typename elem<DT>::T* op = (typename elem<DT>::T*)out + row * ldo + c0;
+        if (DT == ASVD_F32) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                ((uint4*)op)[j] = make_uint4(__float_as_uint(v[4 * j]), __float_as_uint(v[4 * j + 1]), __float_as_uint(v[4 * j + 2]),
+                                             __float_as_uint(v[4 * j + 3]));
+        } else {
+            uint32_t h[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p)
+                h[p] = DT == ASVD_F16 ? ((uint32_t)f32_to_f16_bits(v[2 * p]) | ((uint32_t)f32_to_f16_bits(v[2 * p + 1]) << 16))
+                                      : ((uint32_t)f32_to_bf16_bits(v[2 * p]) | ((uint32_t)f32_to_bf16_bits(v[2 * p + 1]) << 16));
+            ((uint4*)op)[0] = make_uint4(h[0], h[1], h[2], h[3]);
+            ((uint4*)op)[1] = make_uint4(h[4], h[5], h[6], h[7]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (c0 + j < cols) elem<DT>::st(out, row * ldo + c0 + j, v[j]);
+    }
+}
+
+// the CU count of the current device.  Per-call host cost matters at decode size: the count of the first W8_MAX_DEVICES devices is looked up once
+// (relaxed atomics: two threads may both look it up and store the same value); devices beyond that are asked every call
+int w8_cu_count(int* cus_out) {
+    static std::atomic<int> s_cus[W8_MAX_DEVICES];
+    int dev = 0;
+    ASVD_HIP_CHECK(hipGetDevice(&dev));
+    int cus = (dev >= 0 && dev < W8_MAX_DEVICES) ? s_cus[dev].load(std::memory_order_relaxed) : 0;
+    if (!cus) {
+        ASVD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        if (cus < 1) return ASVD_E_HIP;
+        if (dev >= 0 && dev < W8_MAX_DEVICES) s_cus[dev].store(cus, std::memory_order_relaxed);
+    }
+    *cus_out = cus;
+    return ASVD_OK;
+}
+
+// the widest feature tile that still puts a workgroup on every CU (bandwidth-bound: more streams win over fuller MFMA tiles)
+int w8_feature_tile(int nT, int64_t N, int cus) {
+    int ft = 32;
+    while (ft > 8 && nT * ceil_div64(N, ft) < cus) ft /= 2;
+    return ft;
 }
 
 }  // namespace
@@ -248,24 +390,14 @@ int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, con
     if (!x || !q || !scale || !zero || !y) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || ldq < K || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
-    // per-call host cost matters at decode size: the CU count of the first W8_MAX_DEVICES devices is looked up once (relaxed atomics: two
-    // threads may both look it up and store the same value); devices beyond that are asked every call
-    static std::atomic<int> s_cus[W8_MAX_DEVICES];
-    int dev = 0;
-    ASVD_HIP_CHECK(hipGetDevice(&dev));
-    int cus = (dev >= 0 && dev < W8_MAX_DEVICES) ? s_cus[dev].load(std::memory_order_relaxed) : 0;
-    if (!cus) {
-        ASVD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (cus < 1) return ASVD_E_HIP;
-        if (dev >= 0 && dev < W8_MAX_DEVICES) s_cus[dev].store(cus, std::memory_order_relaxed);
-    }
+    int cus = 0;
+    const int st = w8_cu_count(&cus);
+    if (st != ASVD_OK) return st;
     const int nT = (int)((T + 31) / 32);
-    // the widest feature tile that still puts a workgroup on every CU (bandwidth-bound: more streams win over fuller MFMA tiles)
-    int ft = 32;
-    while (ft > 8 && nT * ceil_div64(N, ft) < cus) ft /= 2;
+    const int ft = w8_feature_tile(nT, N, cus);
     const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)q % 16 == 0) && (K % 8 == 0) && (ldq % 16 == 0);
     const int nkfull = vec ? (int)(K / W8_KIT) : 0;
-    hipLaunchKernelGGL(w8_linear_kernel, dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(w8_linear_kernel<8>, dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
                        (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
                        nkfull, vec ? 1 : 0);
     ASVD_HIP_CHECK(hipGetLastError());
@@ -289,6 +421,67 @@ int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float*
                             hipLaunchKernelGGL(w8_dequant_elem_kernel<DT>, dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
                                                (const uint8_t*)q, ldq, scale, zero, rows, cols, out, ldo));
     }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+int64_t asvd_wb_row_bytes(int64_t cols, int bits) { return (cols < 1 || (bits != 4 && bits != 6)) ? -1 : wb_row_bytes(cols, bits); }
+
+int asvd_wb_pack(const void* q, int64_t ldq, int64_t rows, int64_t cols, int bits, void* out, int64_t ld_bytes, void* stream) {
+    if (!q || !out || rows < 1 || cols < 1 || ldq < cols || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
+    if (ld_bytes < wb_row_bytes(cols, bits) || (uintptr_t)out % 4 || ld_bytes % 4) return ASVD_E_BADARG;   // 4-byte stores
+    const int64_t grid = ceil_div64(rows * ((cols + 63) / 64 * 4), W8_THREADS);
+    if (grid > 0x7fffffff) return ASVD_E_BADARG;
+    if (bits == 6)
+        hipLaunchKernelGGL(wb_pack_kernel<6>, dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint8_t*)q, ldq, rows, cols,
+                           (uint8_t*)out, ld_bytes);
+    else
+        hipLaunchKernelGGL(wb_pack_kernel<4>, dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint8_t*)q, ldq, rows, cols,
+                           (uint8_t*)out, ld_bytes);
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+int asvd_wb_dequant(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out,
+                    int out_dtype, int64_t ldo, void* stream) {
+    if (!q || !scale || !zero || !out || rows < 1 || cols < 1 || ldo < cols || !dtype_ok(out_dtype) || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
+    if (ld_bytes < wb_row_bytes(cols, bits) || (uintptr_t)q % 4 || ld_bytes % 4) return ASVD_E_BADARG;   // 4-byte loads
+    const int64_t es = (int64_t)dtype_size(out_dtype);
+    if ((uintptr_t)out % es) return ASVD_E_BADARG;
+    const int vec = (cols % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((ldo * es) % 16 == 0);
+    const int64_t grid = ceil_div64(rows * ((cols + 15) / 16), W8_THREADS);
+    if (grid > 0x7fffffff) return ASVD_E_BADARG;
+    if (bits == 6) {
+        ASVD_DISPATCH_DTYPE(out_dtype, DT,
+                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 6>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec));
+    } else {
+        ASVD_DISPATCH_DTYPE(out_dtype, DT,
+                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 4>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec));
+    }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+int asvd_wb_linear_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, const void* bias,
+                       int64_t N, int64_t K, void* y, void* stream) {
+    if (!x || !q || !scale || !zero || !y || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
+    if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
+    if (ld_bytes < wb_row_bytes(K, bits) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    int cus = 0;
+    const int st = w8_cu_count(&cus);
+    if (st != ASVD_OK) return st;
+    const int nT = (int)((T + 31) / 32);
+    const int ft = w8_feature_tile(nT, N, cus);
+    const dim3 grid((unsigned)ceil_div64(N, ft), (unsigned)nT);
+    if (bits == 6)
+        hipLaunchKernelGGL(w8_linear_kernel<6>, grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q, ld_bytes,
+                           scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1);
+    else
+        hipLaunchKernelGGL(w8_linear_kernel<4>, grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q, ld_bytes,
+                           scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
 }

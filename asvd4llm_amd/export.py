@@ -13,7 +13,9 @@ with `AutoModelForCausalLM.from_pretrained(path, trust_remote_code=True)` as the
 A model whose weights were packed (`--weight_quant_storage packed`: W8Linear modules) is written as it is — the checkpoint then holds
 `<layer>.qweight` (uint8), `.scales`, `.zeros` (fp32) in place of `<layer>.weight` — with `"weight_quant": {"method": "rtn", "bits": b,
 "storage": "uint8"}` in config.json and WITHOUT `auto_map` and the remote-code files, which cannot rebuild packed modules: such a repo loads
-with `load_asvd_repo` only.
+with `load_asvd_repo` only.  A model whose codes are stored at their own width (`--weight_quant_storage bitpacked`: WBLinear modules) is written
+the same way with `<layer>.qbits` (uint8 bitstream rows, modules/wb_linear.py) in place of `.qweight` and `"storage": "bitstream64"`.  One
+model holds one width and one storage form.
 """
 import json
 import os
@@ -23,6 +25,7 @@ import torch.nn as nn
 
 from .modules.svd_linear import SVDLinear
 from .modules.w8_linear import W8Linear
+from .modules.wb_linear import WBLinear, row_bytes
 
 _FAMILIES = {
     # family tag -> (HF config class, HF model class, file stem)
@@ -110,6 +113,26 @@ def packed_layers_of(model):
     return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, W8Linear)}
 
 
+def bitpacked_layers_of(model):
+    """{full layer name: bits} of every WBLinear, in named_modules order"""
+    return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, WBLinear)}
+
+
+def replace_with_bitpacked(model, state, bits, dtype=None):
+    """Swap every module whose checkpoint keys end in `.qbits` for an empty WBLinear.  in_features comes from the module that is there (the base
+    architecture's Linear, or the factor pair built from truncation_ranks); the checkpoint's rows must be the bitstream of that many codes."""
+    for key in [k for k in state if k.endswith(".qbits")]:
+        full_name = key[: -len(".qbits")]
+        parent_name, _, child = full_name.rpartition(".")
+        parent = model.get_submodule(parent_name) if parent_name else model
+        old = getattr(parent, child)
+        if not isinstance(old, nn.Linear) or tuple(state[key].shape) != (old.out_features, row_bytes(old.in_features, bits)):
+            raise ValueError(f"{full_name}: bit-packed weight {tuple(state[key].shape)} ({bits} bits) does not fit {old}")
+        setattr(parent, child, WBLinear(old.in_features, old.out_features, bias=old.bias is not None, bits=bits, weight_dtype=dtype or old.weight.dtype,
+                                        device=old.weight.device))
+    return model
+
+
 def replace_with_packed(model, state, bits=8, dtype=None):
     """Swap every module whose checkpoint keys end in `.qweight` for an empty W8Linear of the checkpoint's shape, so that the packed keys fit."""
     for key in [k for k in state if k.endswith(".qweight")]:
@@ -138,15 +161,19 @@ def save_asvd_repo(model, save_path, tokenizer=None, family=None):
     config = model.config.to_dict()
     ranks = truncation_ranks_of(model)
     config["truncation_ranks"] = ranks
-    packed = packed_layers_of(model)
-    if packed:
+    packed, bitpacked = packed_layers_of(model), bitpacked_layers_of(model)
+    if packed and bitpacked:
+        raise ValueError(f"{len(packed)} uint8-packed next to {len(bitpacked)} bit-packed layers: one model holds one storage form")
+    if packed or bitpacked:
+        storage = "uint8" if packed else "bitstream64"
+        packed = packed or bitpacked
         if len(set(packed.values())) != 1:
             raise ValueError(f"packed layers of several bit widths in one model: {sorted(set(packed.values()))}")
-        config["weight_quant"] = {"method": "rtn", "bits": next(iter(packed.values())), "storage": "uint8"}
+        config["weight_quant"] = {"method": "rtn", "bits": next(iter(packed.values())), "storage": storage}
         config.pop("auto_map", None)
         with open(os.path.join(save_path, "config.json"), "w") as f:
             json.dump(config, f, indent=2)
-        print(f"{len(packed)} packed (uint8) weights: no auto_map / remote-code files written, load with asvd4llm_amd.export.load_asvd_repo")
+        print(f"{len(packed)} packed ({storage}) weights: no auto_map / remote-code files written, load with asvd4llm_amd.export.load_asvd_repo")
         return ranks
     config["auto_map"] = {
         "AutoConfig": f"configuration_asvd_{stem}.ASVD{Fam}Config",
@@ -201,13 +228,17 @@ def load_asvd_repo(path, dtype=torch.float16, device="cpu"):
     replace_with_factor_pairs(model, ranks, dtype=dtype)
     state = _read_state_dict(path)
     wq = raw.get("weight_quant") or {}
-    if any(k.endswith(".qweight") for k in state):
+    if any(k.endswith((".qweight", ".qbits")) for k in state):
         # the codes stand for weights of ONE dtype, the model's at pack time (save_pretrained records it); loading them as another would
         # round every weight once more and take the packed layers off the kernel path
         packed_dtype = raw.get("torch_dtype") or raw.get("dtype")
         if packed_dtype is not None and getattr(torch, str(packed_dtype), None) != dtype:
             raise ValueError(f"{path} holds weights packed from {packed_dtype}; load it with dtype=torch.{packed_dtype} (got {dtype})")
         replace_with_packed(model, state, bits=int(wq.get("bits", 8)), dtype=dtype)
+        if any(k.endswith(".qbits") for k in state):
+            if "bits" not in wq:
+                raise ValueError(f"{path} holds bit-packed weights but config.json does not give their width (weight_quant.bits)")
+            replace_with_bitpacked(model, state, bits=int(wq["bits"]), dtype=dtype)
     missing, unexpected = model.load_state_dict(state, strict=False)
     tied_ok = {"lm_head.weight"} if getattr(cfg, "tie_word_embeddings", False) else set()
     bad_missing = [k for k in missing if k not in tied_ok and not k.endswith("rotary_emb.inv_freq")]

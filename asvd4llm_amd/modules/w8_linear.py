@@ -9,9 +9,9 @@ Not an nn.Linear subclass on purpose: collect_linear_info, the calibration hooks
 must keep ignoring packed ones."""
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
+from .packed_linear import PackedLinear
 
 # Token count up to which forward() takes the kernel: the measured crossover (tools/bench_w8_forward.py --force_kernel --tokens 1,4,16,32,64 on
 # MI355X, profiles/w8_forward.json, DESIGN.md section 4).  Against the fake-quantized fp16 weights through nn.Linear on the Llama-2-7B ASVD-0.9
@@ -21,7 +21,7 @@ from .. import ops
 W8_FORWARD_MAX_TOKENS = 16
 
 
-class W8Linear(nn.Module):
+class W8Linear(PackedLinear):
     """y = x w^T + bias with w held as `qweight` uint8 [out, in], `scales` fp32 [out], `zeros` fp32 [out] (persistent buffers: they are what
     state_dict() and save_pretrained() write) and an optional `bias` buffer in the original dtype."""
 
@@ -48,17 +48,6 @@ class W8Linear(nn.Module):
         self.register_buffer("bias", bias)
         return self
 
-    def _apply(self, fn, *args, **kwargs):
-        # The buffers DEFINE the weight: a dtype cast of the model (.half(), .double(), .to(dtype)) must not touch the fp32 scales and zeros,
-        # and the bias stays in weight_dtype with the weight it belongs to.  Device moves go through.  forward() casts to the input's dtype.
-        keep = {n: getattr(self, n) for n in ("scales", "zeros", "bias") if getattr(self, n) is not None}
-        super()._apply(fn, *args, **kwargs)
-        for n, old in keep.items():
-            new = getattr(self, n)
-            if new.dtype != old.dtype:
-                setattr(self, n, old.to(new.device))
-        return self
-
     def dequantize(self):
         """the weight in weight_dtype.  CUDA: csrc/w8_linear.hip; CPU: the same arithmetic in torch (fp32 subtraction, one fp32 product, one
         rounding)"""
@@ -74,19 +63,11 @@ class W8Linear(nn.Module):
         return self.in_features % 16 == 0 and q.is_contiguous() and q.data_ptr() % 16 == 0
 
     def forward(self, x):
-        tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if (x.is_cuda and x.dtype == torch.float16 and self.weight_dtype == torch.float16 and 0 < tokens <= W8_FORWARD_MAX_TOKENS
-                and (self.bias is None or self.bias.dtype == torch.float16) and not (torch.is_grad_enabled() and x.requires_grad)
-                and self.kernel_rows_ok()):
-            x2d = x.reshape(-1, x.shape[-1])
-            x2d = x2d if x2d.is_contiguous() else x2d.contiguous()
-            if x2d.data_ptr() % 16 == 0:
-                y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias)
-                return y.view(*x.shape[:-1], self.out_features)
-        w, b = self.dequantize(), self.bias
-        if x.dtype != w.dtype:   # a model cast to another dtype: the same weight, converted for the GEMM (exact into a wider type)
-            w, b = w.to(x.dtype), None if b is None else b.to(x.dtype)
-        return F.linear(x, w, b)
+        x2d = self._kernel_input(x, W8_FORWARD_MAX_TOKENS)
+        if x2d is not None:
+            y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias)
+            return y.view(*x.shape[:-1], self.out_features)
+        return self._dense_forward(x)
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, bits={self.bits}, weight_dtype={self.weight_dtype}"

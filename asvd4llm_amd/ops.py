@@ -482,6 +482,84 @@ def w8_dequant(q, scale, zero, dtype, out=None):
     return out
 
 
+def wb_row_bytes(cols, bits):
+    """bytes of a bitstream row of `cols` codes of `bits` (4 or 6) bits: ceil(cols / 64) * 8 * bits (asvd_wb_row_bytes; a host-side query)"""
+    n = L.load().asvd_wb_row_bytes(int(cols), int(bits))
+    if n < 0:
+        raise ValueError(f"bit-packed rows hold 1 or more codes of 4 or 6 bits (got {cols} codes of {bits} bits)")
+    return int(n)
+
+
+def wb_pack(q, bits, out=None):
+    """uint8 codes q [rows, cols] (unit column stride) -> bitstream rows uint8 [rows, wb_row_bytes(cols, bits)] (K13, asvd_wb_pack): code k of
+    a row in bits [bits k, bits (k + 1)) of the row read as one little-endian integer, zero-padded to whole blocks of 64 codes."""
+    lib = L.load(True)
+    _dev(q, "q")
+    if q.dim() != 2 or q.dtype != torch.uint8 or q.stride(1) != 1 or q.shape[0] < 1 or q.shape[1] < 1:
+        raise ValueError(f"wb_pack needs q [rows, cols] uint8 with unit column stride (got {tuple(q.shape)} {q.dtype})")
+    rows, cols = q.shape
+    nb = wb_row_bytes(cols, bits)
+    if out is None:
+        out = torch.empty((rows, nb), dtype=torch.uint8, device=q.device)
+    elif out.shape != (rows, nb) or out.dtype != torch.uint8 or out.stride(1) != 1 or out.device != q.device:
+        raise ValueError(f"wb_pack: out must be [{rows}, {nb}] uint8 with unit column stride on the device of q")
+    with _on(q.device):
+        L.check(lib.asvd_wb_pack(q.data_ptr(), q.stride(0), rows, cols, int(bits), out.data_ptr(), out.stride(0), _stream(q)), "asvd_wb_pack")
+    return out
+
+
+def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None):
+    """the dense weight scale * (code - zero) [rows, cols] in `dtype` (fp16 / bf16 / fp32) from bitstream rows qbits [rows, wb_row_bytes(cols,
+    bits)] (asvd_wb_dequant): value for value w8_dequant on the unpacked codes.  out: optional destination with unit column stride."""
+    lib = L.load(True)
+    _dev(qbits, "qbits")
+    if qbits.dim() != 2 or qbits.dtype != torch.uint8 or qbits.stride(1) != 1 or dtype not in _DT:
+        raise ValueError(f"wb_dequant needs qbits [rows, row bytes] uint8 with unit column stride and a float dtype (got {tuple(qbits.shape)} "
+                         f"{qbits.dtype}, {dtype})")
+    rows, cols = qbits.shape[0], int(cols)
+    if qbits.shape[1] != wb_row_bytes(cols, bits):
+        raise ValueError(f"wb_dequant: {tuple(qbits.shape)} is not the bitstream of [{rows}, {cols}] codes of {bits} bits")
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
+            or not zero.is_contiguous() or scale.device != qbits.device or zero.device != qbits.device:
+        raise ValueError("wb_dequant needs scale / zero [rows] fp32 contiguous on the device of qbits")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=dtype, device=qbits.device)
+    elif out.shape != (rows, cols) or out.dtype != dtype or out.stride(1) != 1 or out.device != qbits.device:
+        raise ValueError(f"wb_dequant: out must be [{rows}, {cols}] {dtype} with unit column stride on the device of qbits")
+    if rows == 0:
+        return out
+    with _on(qbits.device):
+        L.check(lib.asvd_wb_dequant(qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(), rows, cols, out.data_ptr(),
+                                    _DT[dtype], out.stride(0), _stream(qbits)), "asvd_wb_dequant")
+    return out
+
+
+def wb_linear(x2d, qbits, bits, scale, zero, bias=None):
+    """w8_linear on bitstream rows (K13, asvd_wb_linear_f16): x2d [T <= 256, K] fp16 contiguous, K % 16 == 0, qbits [N, wb_row_bytes(K, bits)]
+    uint8, scale / zero [N] fp32, bias [N] fp16 or None; x2d and the rows 16-byte aligned.  The bits of w8_linear on the same codes."""
+    lib = L.load(True)
+    _dev(x2d, "x")
+    if x2d.dim() != 2 or qbits.dim() != 2 or x2d.dtype != torch.float16 or qbits.dtype != torch.uint8 or not x2d.is_contiguous() or qbits.stride(1) != 1:
+        raise ValueError(f"wb_linear needs x [T, K] fp16 contiguous and qbits [N, row bytes] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, "
+                         f"{tuple(qbits.shape)} {qbits.dtype})")
+    T, K = x2d.shape
+    N = qbits.shape[0]
+    if K < 1 or K % 16 or qbits.shape[1] != wb_row_bytes(K, bits) or not 1 <= T <= W8_MAX_TOKENS:
+        raise ValueError(f"wb_linear: x {tuple(x2d.shape)} against qbits {tuple(qbits.shape)} of {bits}-bit codes; K % 16 == 0, 1 <= tokens <= {W8_MAX_TOKENS}")
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != N or zero.numel() != N or not scale.is_contiguous() \
+            or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
+        raise ValueError("wb_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
+    if qbits.device != x2d.device or scale.device != x2d.device or zero.device != x2d.device or (bias is not None and bias.device != x2d.device):
+        raise ValueError("wb_linear: all tensors must live on the device of x")
+    if x2d.data_ptr() % 16 or qbits.data_ptr() % 16 or qbits.stride(0) % 16:
+        raise ValueError("wb_linear needs x and the rows of qbits 16-byte aligned")
+    y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
+    with _on(x2d.device):
+        L.check(lib.asvd_wb_linear_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
+                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_wb_linear_f16")
+    return y
+
+
 PROFILE_CLASSES = ["pack", "sgram", "evd", "supdate", "finalize", "snapshot", "gram1", "update1", "supgram"]
 
 

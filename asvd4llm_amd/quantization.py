@@ -4,13 +4,15 @@ The reference's `rtn_quant_sequential(model, wbits)` walks the decoder blocks an
 (`find_layers`, which recurses into SVDLinear, so ALinear and BLinear are both quantized), replaces `weight.data` by the per-row
 round-to-nearest fake quantization of the weight, in the weight's own dtype.  lm_head and the embeddings sit outside the blocks and
 are left alone.  Here the weights of one block go through ONE batched launch (ops.rtn_quant_batched); the arithmetic is the
-reference's bit for bit.  `rtn_pack_sequential` is the same step with the weights kept as uint8 codes (modules/w8_linear.py).  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
+reference's bit for bit.  `rtn_pack_sequential` is the same step with the weights kept as uint8 codes (modules/w8_linear.py) or, for 6 and 4 bits, as codes of their own
+width (modules/wb_linear.py).  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from .modules.svd_linear import SVDLinear
 from .modules.w8_linear import W8Linear
+from .modules.wb_linear import WB_BITS, WBLinear
 from .sweep_eval import find_decoder_blocks
 
 
@@ -71,13 +73,19 @@ def _set_submodule(root, name, new):
 
 
 @torch.no_grad()
-def rtn_pack_sequential(model, wbits):
+def rtn_pack_sequential(model, wbits, storage="bytes"):
     """rtn_quant_sequential with the result kept PACKED: per decoder block one batched launch that also emits the uint8 codes and the per-row
     fp32 scale / zero, and every target nn.Linear replaced by a W8Linear holding them (one byte per weight for any wbits <= 8; the bias is
     kept as it is).  The packed layer stands for exactly the fake-quantized weight: W8Linear.dequantize() is the `out` of the launch, bit
     for bit.  That is checked on the device for every tensor before it is replaced; a tensor stays an nn.Linear — fake-quantized, or
     unchanged when the kernel flags a row with scale 0, exactly as rtn_quant_sequential leaves it — when its fake-quantized weight holds a
-    non-finite value or its codes do not reproduce it (one flag read-back per block).  Returns the number of weights packed."""
+    non-finite value or its codes do not reproduce it (one flag read-back per block).  Returns the number of weights packed.
+    storage="bits" (wbits 6 or 4 only): the codes of the launch are packed to their own width (ops.wb_pack), the byte codes released and the
+    layer becomes a WBLinear; the check is the same, on what ops.wb_dequant reads back from the bit-packed rows."""
+    if storage not in ("bytes", "bits"):
+        raise ValueError(f"storage must be 'bytes' or 'bits' (got {storage!r})")
+    if storage == "bits" and int(wbits) not in WB_BITS:
+        raise ValueError(f"bit-packed storage holds codes of 4 or 6 bits (got wbits={wbits}); 8-bit codes are already one per byte")
     blocks_name, blocks = find_decoder_blocks(model)
     if blocks is None:
         raise ValueError("no decoder blocks (nn.ModuleList of Linear-holding modules) found in the model")
@@ -90,27 +98,34 @@ def rtn_pack_sequential(model, wbits):
         if not subset:
             continue
         res = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, want_params=True)
-        bad = []
+        bad, packed = [], []
         for (_, lin), (out, q, scale, zero, flagged) in zip(subset, res):
+            packed.append(ops.wb_pack(q, wbits) if storage == "bits" and not flagged else None)
             if flagged:
                 bad.append(torch.ones((), dtype=torch.bool, device=q.device))
             else:
-                back = ops.w8_dequant(q, scale, zero, out.dtype)
+                back = (ops.wb_dequant(packed[-1], wbits, q.shape[1], scale, zero, out.dtype) if storage == "bits"
+                        else ops.w8_dequant(q, scale, zero, out.dtype))
                 bits_t = torch.int32 if out.dtype == torch.float32 else torch.int16
                 bad.append(~torch.isfinite(out).all() | (back.view(bits_t) != out.view(bits_t)).any())
         bad = torch.stack(bad).tolist()   # the one read-back of the block
-        for (name, lin), (out, q, scale, zero, flagged), keep in zip(subset, res, bad):
+        for (name, lin), (out, q, scale, zero, flagged), qbits, keep in zip(subset, res, packed, bad):
             nbytes = lin.weight.numel() * lin.weight.element_size()
             if keep:
                 lin.weight.data = out   # the input itself when flagged (ops.rtn_quant_batched)
                 continue
             bias = lin.bias.data if lin.bias is not None else None
-            _set_submodule(block, name, W8Linear.from_codes(q, scale, zero, bias, wbits, out.dtype))
+            if storage == "bits":
+                new = WBLinear.from_bits(qbits, q.shape[1], scale, zero, bias, wbits, out.dtype)
+            else:
+                new = W8Linear.from_codes(q, scale, zero, bias, wbits, out.dtype)
+            _set_submodule(block, name, new)
             n_packed += 1
             bytes_before += nbytes
-            bytes_after += q.numel() + 4 * (scale.numel() + zero.numel())
+            bytes_after += (qbits if storage == "bits" else q).numel() + 4 * (scale.numel() + zero.numel())
+        del res, packed   # storage="bits": the byte codes go with them
         for m in block.modules():
             if isinstance(m, SVDLinear):
                 m.refresh_fused()
-    print(f"rtn int{wbits} packed: {n_packed} weights in {len(blocks)} blocks, {bytes_before} -> {bytes_after} bytes")
+    print(f"rtn int{wbits} {'bit-packed' if storage == 'bits' else 'packed'}: {n_packed} weights in {len(blocks)} blocks, {bytes_before} -> {bytes_after} bytes")
     return n_packed

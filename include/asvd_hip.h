@@ -308,6 +308,32 @@ int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float*
                     int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K13  The codes of K11 stored at their own width, bits = 6 or 4 (the quantizer's range 0 .. 2^bits - 1 needs no more).
+ * Format ("bitstream64", an on-disk format): a row of K codes is a little-endian bitstream, code k in bits [bits k, bits (k + 1)) of the row
+ *   read as one little-endian integer, zero-padded to whole blocks of 64 codes.  A block is 8 bits bytes (48 at 6 bits, 32 at 4), a row
+ *   asvd_wb_row_bytes(K, bits) = ceil(K / 64) * 8 * bits bytes: a multiple of 16, so with a 16-byte-aligned base and leading dimension every
+ *   block starts 16-byte aligned.  At 6 bits codes 5 and 10 of every 16 cross a 32-bit word, at 4 bits none does.  Padding codes are 0 and never
+ *   part of the weight.
+ * asvd_wb_row_bytes:  host-only query; -1 for bits other than 4 and 6 or cols < 1.
+ * asvd_wb_pack:  q [rows, ldq] uint8 codes (ldq >= cols) -> out [rows, ld_bytes] bitstream rows (ld_bytes >= row bytes; out and ld_bytes multiples
+ *   of 4).  Codes are masked to `bits` bits (the quantizer emits none beyond).  Bytes of a row beyond its row bytes are not written.  Asynchronous.
+ * asvd_wb_dequant:  out [rows, cols] (ldo) in out_dtype (F32 / F16 / BF16) from the bitstream rows q (q and ld_bytes multiples of 4), value for
+ *   value asvd_w8_dequant on the unpacked codes: fp32 subtraction, one fp32 product, one rounding.  Any cols >= 1, any destination aligned to its
+ *   element; nothing outside [rows, cols] is written.  Asynchronous.
+ * asvd_wb_linear_f16:  asvd_w8_linear_f16 on bitstream rows: the same tiles, the same split of k over the waves, the same order of every sum,
+ *   the codes cut out of three (6 bits) or two (4 bits) 16-byte loads per lane and iteration instead of four.  The result has the BITS of
+ *   asvd_w8_linear_f16 on the same codes, scale, zero and bias.  K % 16 == 0 only; x, q and ld_bytes 16-byte aligned; y and bias 2-byte aligned;
+ *   1 <= T <= ASVD_W8_MAX_TOKENS.  Asynchronous.
+ * Bad arguments (NULL, other widths, T out of range, K % 16 != 0, short leading dimensions, misaligned x / q / y / out) return ASVD_E_BADARG
+ * before any device call. */
+int64_t asvd_wb_row_bytes(int64_t cols, int bits);
+int asvd_wb_pack(const void* q, int64_t ldq, int64_t rows, int64_t cols, int bits, void* out, int64_t ld_bytes, void* stream);
+int asvd_wb_dequant(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out,
+                    int out_dtype, int64_t ldo, void* stream);
+int asvd_wb_linear_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                       const void* bias, int64_t N, int64_t K, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

@@ -11,7 +11,11 @@ alternating, device events around each pass, median / min / max / spread (max - 
 pass is bound by the host (Python and launch cost per layer, for both paths), so every figure is reported twice: "eager" as a user's forward runs,
 and "graph" with one pass of each path captured into a device graph and replayed (no host work inside the timed window: what the device does).  (b) also gets its
 algorithmic bytes (codes + 8 bytes per row + activations in and out), GB/s and the share of the 8 TB/s HBM spec, and the largest difference
-between the outputs of (a) and (b) over all layers, relative to the largest output."""
+between the outputs of (a) and (b) over all layers, relative to the largest output.
+--code_bits 6 | 4 quantizes to that width and adds
+  (c) WBLinear modules holding the same codes at their own width (--weight_quant_storage bitpacked; csrc/w8_linear.hip, K13),
+timed in the same alternation and reported under "bitpacked" with the columns of (b), plus its time over (b)'s and whether it is slower than
+(b) by more than (b)'s own spread.  Without --code_bits the output is what it was."""
 import argparse
 import json
 import os
@@ -25,14 +29,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from asvd4llm_amd import _lib as L  # noqa: E402
 from asvd4llm_amd import ops  # noqa: E402
 from asvd4llm_amd.modules import w8_linear as W  # noqa: E402
+from asvd4llm_amd.modules import wb_linear as WB  # noqa: E402
 from bench_rtn import HBM_SPEC, median, shape_sets  # noqa: E402
 
 TOKENS = (1, 4, 16, 64)
 
 
-def build_set(blocks, factored, bits, dev, seed):
-    """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear) stages applied in order (BLinear, ALinear for a factored
-    layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
+def build_set(blocks, factored, bits, dev, seed, bitpacked=False):
+    """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear[, WBLinear]) stages applied in order (BLinear, ALinear for a
+    factored layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
     g = torch.Generator(device=dev).manual_seed(seed)
     out = []
     for blk in blocks:
@@ -43,7 +48,10 @@ def build_set(blocks, factored, bits, dev, seed):
             assert not flagged
             lin = nn.Linear(fake.shape[1], fake.shape[0], bias=False, device="meta")
             lin.weight = nn.Parameter(fake, requires_grad=False)
-            stages.append((lin, W.W8Linear.from_codes(q, scale, zero, None, bits, torch.float16)))
+            stage = (lin, W.W8Linear.from_codes(q, scale, zero, None, bits, torch.float16))
+            if bitpacked:
+                stage += (WB.WBLinear.from_codes(q, scale, zero, None, bits, torch.float16),)
+            stages.append(stage)
         out.append([[stages[i + 1], stages[i]] for i in range(0, len(stages), 2)] if factored else [[s] for s in stages])
     return out
 
@@ -58,19 +66,19 @@ def run_pass(layers, xs, which):
     return y
 
 
-def timed_pair(layers, xs, iters, warmup, graph):
-    ta, tb = [], []
+def timed_paths(layers, xs, iters, warmup, graph, npaths=2):
+    times = [[] for _ in range(npaths)]
     if graph:   # one pass of each path, captured once (a linear chain of launches) and replayed
         run = []
-        for which in (0, 1):
+        for which in range(npaths):
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr):
                 run_pass(layers, xs, which)
             run.append(gr.replay)
     else:
-        run = [lambda: run_pass(layers, xs, 0), lambda: run_pass(layers, xs, 1)]
+        run = [lambda which=which: run_pass(layers, xs, which) for which in range(npaths)]
     for it in range(warmup + iters):
-        for which, ts in ((0, ta), (1, tb)):
+        for which, ts in enumerate(times):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             run[which]()
@@ -78,17 +86,17 @@ def timed_pair(layers, xs, iters, warmup, graph):
             e1.synchronize()
             if it >= warmup:
                 ts.append(e0.elapsed_time(e1))
-    return ta, tb
+    return times
 
 
 @torch.no_grad()
-def max_difference(layers, xs):
+def max_difference(layers, xs, which=1):
     worst, top = 0.0, 0.0
     for blk in layers:
         for layer in blk:
             ya = yb = xs[layer[0][0].in_features]
-            for lin, packed in layer:
-                ya, yb = lin(ya), packed(yb)
+            for stage in layer:
+                ya, yb = stage[0](ya), stage[which](yb)
             worst = max(worst, (ya.float() - yb.float()).abs().max().item())
             top = max(top, ya.float().abs().max().item())
     return worst, top
@@ -100,27 +108,43 @@ def stats(ts):
 
 
 def run_set(blocks, factored, args, dev):
-    layers = build_set(blocks, factored, args.bits, dev, args.seed)
+    bitpacked = args.code_bits != 8
+    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked)
     stages = [s for blk in layers for layer in blk for s in layer]
-    code_bytes = sum(p.qweight.numel() + 8 * p.out_features for _, p in stages)
-    fp16_bytes = sum(2 * lin.weight.numel() for lin, _ in stages)
+    code_bytes = sum(s[1].qweight.numel() + 8 * s[1].out_features for s in stages)
+    fp16_bytes = sum(2 * s[0].weight.numel() for s in stages)
     res = {"launches_per_pass": len(stages), "fp16_weight_bytes": fp16_bytes, "packed_weight_bytes": code_bytes, "tokens": {}}
+    if bitpacked:
+        bit_bytes = sum(s[2].qbits.numel() + 8 * s[2].out_features for s in stages)
+        res["bitpacked_weight_bytes"] = bit_bytes
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
     for T in args.tokens:
         xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
-        act_bytes = sum(2 * T * (lin.in_features + lin.out_features) for lin, _ in stages)
+        act_bytes = sum(2 * T * (s[0].in_features + s[0].out_features) for s in stages)
         nbytes = code_bytes + act_bytes
         diff, top = max_difference(layers, xs)
         rec = {"kernel_dispatched": T <= W.W8_FORWARD_MAX_TOKENS, "packed_bytes": nbytes, "max_abs_diff": diff, "max_abs_output": top,
                "max_rel_diff": diff / top if top else 0.0}
+        if bitpacked:
+            diff_c, _ = max_difference(layers, xs, 2)
+            rec.update({"bitpacked_kernel_dispatched": T <= WB.WB_FORWARD_MAX_TOKENS, "bitpacked_bytes": bit_bytes + act_bytes,
+                        "bitpacked_max_abs_diff": diff_c, "bitpacked_max_rel_diff": diff_c / top if top else 0.0})
         for mode in ("eager", "graph"):
-            ta, tb = timed_pair(layers, xs, args.iters, args.warmup, mode == "graph")
-            a, b = stats(ta), stats(tb)
+            times = timed_paths(layers, xs, args.iters, args.warmup, mode == "graph", 3 if bitpacked else 2)
+            a, b = stats(times[0]), stats(times[1])
             rec[mode] = {"fp16_linear": a, "packed": b, "packed_over_fp16": round(b["median_ms"] / a["median_ms"], 4),
                          "packed_not_slower": b["median_ms"] <= a["median_ms"] + a["spread_ms"],
                          "packed_gbps": round(nbytes / (b["median_ms"] * 1e-3) / 1e9, 1),
                          "packed_frac_of_hbm_spec": round(nbytes / (b["median_ms"] * 1e-3) / HBM_SPEC, 4),
                          "fp16_gbps": round((fp16_bytes + act_bytes) / (a["median_ms"] * 1e-3) / 1e9, 1)}
+            if bitpacked:   # against (b), the one-byte-per-code pass of the same run; (b)'s spread is the noise floor of that comparison
+                c = stats(times[2])
+                rec[mode].update({"bitpacked": c, "bitpacked_over_fp16": round(c["median_ms"] / a["median_ms"], 4),
+                                  "bitpacked_over_packed": round(c["median_ms"] / b["median_ms"], 4),
+                                  "bitpacked_minus_packed_ms": round(c["median_ms"] - b["median_ms"], 4),
+                                  "bitpacked_not_slower_than_packed": c["median_ms"] <= b["median_ms"] + b["spread_ms"],
+                                  "bitpacked_gbps": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / 1e9, 1),
+                                  "bitpacked_frac_of_hbm_spec": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / HBM_SPEC, 4)})
         res["tokens"][str(T)] = rec
     return res
 
@@ -128,6 +152,8 @@ def run_set(blocks, factored, args, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bits", type=int, default=8)
+    ap.add_argument("--code_bits", type=int, default=8, choices=[8, 6, 4],
+                    help="6 / 4: quantize to that width (overrides --bits) and add path (c), WBLinear on the codes stored at their own width")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=233)
@@ -137,13 +163,20 @@ def main():
     args = ap.parse_args()
     if args.iters < 10:
         ap.error("--iters must be at least 10")
+    if args.code_bits != 8:
+        args.bits = args.code_bits
+        if args.force_kernel and args.rank_align % 16:
+            ap.error("--force_kernel with --code_bits 6 / 4 needs --rank_align to be a multiple of 16: the bit-packed kernel takes K % 16 == 0 only")
     L.load(require_device=True)
     dev = torch.device("cuda", 0)
     if args.force_kernel:
         W.W8_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
         W.W8Linear.kernel_rows_ok = lambda self: True   # rows that allow no 16-byte loads too (--rank_align 1)
+        WB.WB_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
     res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
            "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
+    if args.code_bits != 8:
+        res.update({"code_bits": args.code_bits, "bitpacked_dispatch_max_tokens": WB.WB_FORWARD_MAX_TOKENS})
     for name, blocks in shape_sets(0.9, args.rank_align).items():
         res["sets"][name] = run_set(blocks, "asvd" in name, args, dev)
         torch.cuda.empty_cache()
