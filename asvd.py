@@ -29,30 +29,34 @@ def build_model(args):
 
 def run_weight_quant(model, args):
     """--weight_quant (asvd.py:49-58 of the reference), after the search and the factor gather.  Under --dist with --gather_factors rank0 only
-    rank 0 holds the complete model; the other ranks stop before evaluation, so only rank 0 quantizes.  The result is per row, so it does not
-    depend on which rank computes it."""
+    rank 0 holds the complete model; the other ranks stop before evaluation, so only rank 0 quantizes.  The result is per row (or per group of
+    a row, --weight_quant_group_size), so it does not depend on which rank computes it."""
     if args.weight_quant.startswith("awq"):
         raise NotImplementedError(f"--weight_quant {args.weight_quant} needs the `awq` package (AutoAWQ), which this build does not provide; "
-                                  "use rtn_int8 or rtn_int6")
-    bits = {"rtn_int8": 8, "rtn_int6": 6}[args.weight_quant]
+                                  "use rtn_int8, rtn_int6 or rtn_int4 (with --weight_quant_group_size 128)")
+    bits = {"rtn_int8": 8, "rtn_int6": 6, "rtn_int4": 4}[args.weight_quant]
     storage = getattr(args, "weight_quant_storage", "fake")
+    group = int(getattr(args, "weight_quant_group_size", 0) or 0)
+    if group not in (0, 64, 128):
+        raise ValueError(f"--weight_quant_group_size must be 0, 64 or 128 (got {group})")
+    kw = {"group_size": group} if group else {}   # per row: exactly the calls made before the flag existed
     if storage == "bitpacked" and bits == 8:
         raise ValueError("--weight_quant_storage bitpacked with rtn_int8: 8-bit codes are already one per byte: use packed")
     if args.dist and args.gather_factors == "rank0" and int(os.environ.get("RANK", "0")) != 0:
         return
     if storage == "bitpacked":
-        # ... with the codes stored at their own width (WBLinear modules: 6 bits per weight; the same weights and, at decode sizes, the same
-        # output bits as `packed`)
+        # ... with the codes stored at their own width (WBLinear modules: 6 or 4 bits per weight; the same weights and, at decode sizes, the
+        # same output bits as `packed`)
         from asvd4llm_amd.quantization import rtn_pack_sequential
-        rtn_pack_sequential(model, bits, storage="bits")
+        rtn_pack_sequential(model, bits, storage="bits", **kw)
         return
     if storage == "packed":
         # the same quantization with the weights kept as uint8 codes (W8Linear modules, W8A16 forward kernel at decode sizes)
         from asvd4llm_amd.quantization import rtn_pack_sequential
-        rtn_pack_sequential(model, bits)
+        rtn_pack_sequential(model, bits, **kw)
         return
     from asvd4llm_amd.quantization import rtn_quant_sequential
-    rtn_quant_sequential(model, bits)
+    rtn_quant_sequential(model, bits, **kw)
 
 
 def main(args):
@@ -135,13 +139,17 @@ def build_parser():
                         help="scaling method")
     parser.add_argument("--sensitivity_metric", type=str, default="ppl", choices=["ppl", "stable_rank"], help="search metric")
     parser.add_argument("--use_cache", action="store_true", help="use cached calibration results")
-    parser.add_argument("--weight_quant", type=str, default="none", choices=["none", "rtn_int8", "rtn_int6", "awq_int8", "awq_int4"],
+    parser.add_argument("--weight_quant", type=str, default="none", choices=["none", "rtn_int8", "rtn_int6", "rtn_int4", "awq_int8", "awq_int4"],
                         help="weight quantization method")
     parser.add_argument("--weight_quant_storage", type=str, default="fake", choices=["fake", "packed", "bitpacked"],
-                        help="rtn_int8 / rtn_int6: `fake` writes the quantized weights back in their dtype (the reference's behaviour); `packed` keeps "
+                        help="rtn_int8 / rtn_int6 / rtn_int4: `fake` writes the quantized weights back in their dtype (the reference's behaviour); `packed` keeps "
                              "them as uint8 codes with per-row fp32 scale and zero (one byte per weight, also for int6) and runs decode-sized "
-                             "inputs on the W8A16 kernel; `bitpacked` (rtn_int6 only) stores the codes at 6 bits per weight and runs the kernel that unpacks "
-                             "them in registers; all three stand for the same weights bit for bit")
+                             "inputs on the W8A16 kernel; `bitpacked` (rtn_int6 / rtn_int4) stores the codes at 6 / 4 bits per weight and runs the kernel "
+                             "that unpacks them in registers; all three stand for the same weights bit for bit")
+    parser.add_argument("--weight_quant_group_size", type=int, default=0, choices=[0, 64, 128],
+                        help="rtn_*: 0 keeps one scale and zero per output row (the reference's RTN); 64 / 128 keep one pair per group of that many "
+                             "input columns (8 bytes per group: 4.5 bits per weight for rtn_int4 with 128), which about halves the quantization "
+                             "error of the ASVD factor pairs and is what makes rtn_int4 usable; valid with every storage")
     parser.add_argument("--eval_mmlu", action="store_true", help="evaluate mmlu")
     parser.add_argument("--eval_ppl", default="wikitext2,ptb", type=str)
     parser.add_argument("--eval_tasks", type=str, default="")

@@ -55,6 +55,13 @@ SIGNATURES = {
     "asvd_wb_pack": (_i, [_vp, _i64, _i64, _i64, _i, _vp, _i64, _vp]),
     "asvd_wb_dequant": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _vp, _i, _i64, _vp]),
     "asvd_wb_linear_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_rtn_quant_grouped": (_i, [_vp, _i, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
+    "asvd_rtn_quant_grouped_batched": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64), _i,
+                                            _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i64]),
+    "asvd_w8_linear_grouped_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_w8_dequant_grouped": (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i64, _vp]),
+    "asvd_wb_dequant_grouped": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i64, _vp]),
+    "asvd_wb_linear_grouped_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "asvd_fro_worksize": (_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

@@ -27,8 +27,8 @@ constexpr int RTN_MAX_BATCH = 16;    // tensors per launch (table size); longer 
 struct RtnTensor {
     const void* in;
     void* out;
-    float* scale;      // [rows] or NULL
-    float* zero;       // [rows] or NULL
+    float* scale;      // [rows] ([rows, ng] when grouped) or NULL
+    float* zero;       // likewise
     uint8_t* codes;    // [rows, cols] contiguous or NULL
     int* flag;         // OR-ed with 1 when a row's scale is 0
     int64_t row0;      // first workgroup of this tensor
@@ -37,6 +37,8 @@ struct RtnTensor {
     int vec_ok;        // in / out rows 16-byte aligned and cols a multiple of the vector width
     int resident;      // the row fits the registers of its threads
     int per_wave;      // one wave per row (else one workgroup per row)
+    int group;         // K14: 0, or the group size (64 / 128): the unit of work is (row, group) and always takes one wave
+    int64_t ng;        // groups per row, ceil(cols / group)
 };
 
 struct RtnTable {
@@ -163,16 +165,16 @@ __device__ __forceinline__ void group_minmax(float& mn, float& mx, float* red) {
     }
 }
 
-// one row quantized by G threads (tid = 0..G-1 within the group)
+// one unit quantized by G threads (tid = 0..G-1 within the group): the `cols` elements of row `row` from column c0 on (the whole row, or one
+// group of it), whose scale and zero go to index sidx
 template <int DT, int G>
-__device__ __forceinline__ void rtn_row(const RtnTensor& T, int64_t row, int tid, float maxq, float* red) {
+__device__ __forceinline__ void rtn_row(const RtnTensor& T, int64_t row, int64_t c0, int64_t cols, int64_t sidx, int tid, float maxq, float* red) {
     constexpr int VEC = rtn_vec<DT>::VEC;
-    const int64_t cols = T.cols;
     const int64_t nvec = (cols + VEC - 1) / VEC;
     const bool vec_ok = T.vec_ok != 0;
-    const void* src = (const char*)T.in + row * T.ldi * (int64_t)sizeof(typename elem<DT>::T);
-    void* dst = (char*)T.out + row * T.ldo * (int64_t)sizeof(typename elem<DT>::T);
-    uint8_t* codes_row = T.codes ? T.codes + row * cols : nullptr;
+    const void* src = (const char*)T.in + (row * T.ldi + c0) * (int64_t)sizeof(typename elem<DT>::T);
+    void* dst = (char*)T.out + (row * T.ldo + c0) * (int64_t)sizeof(typename elem<DT>::T);
+    uint8_t* codes_row = T.codes ? T.codes + row * T.cols + c0 : nullptr;
     float mn = __builtin_inff(), mx = -__builtin_inff();
     uint4 held[RTN_NV];
     if (T.resident) {
@@ -207,8 +209,8 @@ __device__ __forceinline__ void rtn_row(const RtnTensor& T, int64_t row, int tid
     const float scale = (xmax - xmin) / maxq;
     const float zero = rintf(-xmin / scale);
     if (tid == 0) {
-        if (T.scale) T.scale[row] = scale;
-        if (T.zero) T.zero[row] = zero;
+        if (T.scale) T.scale[sidx] = scale;
+        if (T.zero) T.zero[sidx] = zero;
         if (scale == 0.0f) atomicOr(T.flag, 1);
     }
     if (scale == 0.0f) {
@@ -255,21 +257,28 @@ __global__ __launch_bounds__(RTN_THREADS) void rtn_quant_kernel(const RtnTable t
     for (int i = 1; i < RTN_MAX_BATCH; ++i)
         if (i < tab.n && g >= tab.t[i].row0) T = tab.t[i];
     if (T.per_wave) {  // rows of up to 64 x RTN_NV vectors: one wave per row, RTN_THREADS / 64 rows per workgroup, no barrier
-        const int64_t row = (g - T.row0) * (RTN_THREADS / 64) + (threadIdx.x >> 6);
+        const int64_t unit = (g - T.row0) * (RTN_THREADS / 64) + (threadIdx.x >> 6);
+        // K14: unit = row * ng + group; the group's columns start at group * G and the last group of a row holds what is left
+        int64_t row = unit, c0 = 0, cols = T.cols;
+        if (T.group) {
+            row = unit / T.ng;
+            c0 = (unit - row * T.ng) * T.group;
+            cols = cols - c0 < T.group ? cols - c0 : (int64_t)T.group;
+        }
         if (row >= T.rows) return;
         const int lane = threadIdx.x & 63;
         switch (T.dtype) {
-            case ASVD_F32: rtn_row<ASVD_F32, 64>(T, row, lane, tab.maxq, red); break;
-            case ASVD_F16: rtn_row<ASVD_F16, 64>(T, row, lane, tab.maxq, red); break;
-            default: rtn_row<ASVD_BF16, 64>(T, row, lane, tab.maxq, red); break;
+            case ASVD_F32: rtn_row<ASVD_F32, 64>(T, row, c0, cols, unit, lane, tab.maxq, red); break;
+            case ASVD_F16: rtn_row<ASVD_F16, 64>(T, row, c0, cols, unit, lane, tab.maxq, red); break;
+            default: rtn_row<ASVD_BF16, 64>(T, row, c0, cols, unit, lane, tab.maxq, red); break;
         }
         return;
     }
     const int64_t row = g - T.row0;
     switch (T.dtype) {
-        case ASVD_F32: rtn_row<ASVD_F32, RTN_THREADS>(T, row, threadIdx.x, tab.maxq, red); break;
-        case ASVD_F16: rtn_row<ASVD_F16, RTN_THREADS>(T, row, threadIdx.x, tab.maxq, red); break;
-        default: rtn_row<ASVD_BF16, RTN_THREADS>(T, row, threadIdx.x, tab.maxq, red); break;
+        case ASVD_F32: rtn_row<ASVD_F32, RTN_THREADS>(T, row, 0, T.cols, row, threadIdx.x, tab.maxq, red); break;
+        case ASVD_F16: rtn_row<ASVD_F16, RTN_THREADS>(T, row, 0, T.cols, row, threadIdx.x, tab.maxq, red); break;
+        default: rtn_row<ASVD_BF16, RTN_THREADS>(T, row, 0, T.cols, row, threadIdx.x, tab.maxq, red); break;
     }
 }
 
@@ -277,13 +286,10 @@ bool rtn_args_ok(const void* w, int dtype, int64_t rows, int64_t cols, int64_t l
     return w && out && rows >= 1 && cols >= 1 && ldw >= cols && ldo >= cols && dtype_ok(dtype);
 }
 
-}  // namespace
-
-extern "C" {
-
-int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
-                           const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
-                           float* const* zero_host, void* const* codes_host, int* flags, void* stream) {
+// group: 0 (one scale and zero per row) or 64 / 128 (K14: per group of that many columns)
+int rtn_launch_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
+                       const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
+                       float* const* zero_host, void* const* codes_host, int group, int* flags, void* stream) {
     if (batch < 1 || !w_host || !dtype_host || !rows_host || !cols_host || !ldw_host || !out_host || !ldo_host || !flags) return ASVD_E_BADARG;
     if (bits < 1 || bits > 8) return ASVD_E_BADARG;
     for (int b = 0; b < batch; ++b)
@@ -314,16 +320,44 @@ int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtyp
             T.dtype = dt;
             T.vec_ok = ((uintptr_t)T.in % 16 == 0) && ((uintptr_t)T.out % 16 == 0) && ((T.ldi * es) % 16 == 0) && ((T.ldo * es) % 16 == 0) &&
                        (T.cols % vec == 0);
-            const int64_t nvec = ceil_div64(T.cols, vec);
-            T.per_wave = nvec <= (int64_t)RTN_NV * 64;
+            T.group = group;
+            T.ng = group ? ceil_div64(T.cols, group) : 1;   // a group starts 16-byte aligned in an aligned row: vec_ok is the row's
+            const int64_t nvec = ceil_div64(group ? (int64_t)group : T.cols, vec);
+            T.per_wave = nvec <= (int64_t)RTN_NV * 64;      // a group is at most 32 vectors: always
             T.resident = nvec <= (int64_t)RTN_NV * (T.per_wave ? 64 : RTN_THREADS);
-            row0 += T.per_wave ? ceil_div64(T.rows, RTN_THREADS / 64) : T.rows;
+            if (group && T.rows > 0x7fffffffffff / T.ng) return ASVD_E_BADARG;
+            row0 += T.per_wave ? ceil_div64(T.rows * T.ng, RTN_THREADS / 64) : T.rows;
         }
         if (row0 > 0x7fffffff) return ASVD_E_BADARG;
         rtn_quant_kernel<<<(unsigned)row0, RTN_THREADS, 0, st>>>(tab);
         ASVD_HIP_CHECK(hipGetLastError());
     }
     return ASVD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
+                           const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
+                           float* const* zero_host, void* const* codes_host, int* flags, void* stream) {
+    return rtn_launch_batched(batch, w_host, dtype_host, rows_host, cols_host, ldw_host, bits, out_host, ldo_host, scale_host, zero_host, codes_host,
+                              0, flags, stream);
+}
+
+int asvd_rtn_quant_grouped_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
+                                   const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
+                                   float* const* zero_host, void* const* codes_host, int* flags, void* stream, int64_t group) {
+    if (group != 64 && group != 128) return ASVD_E_BADARG;
+    return rtn_launch_batched(batch, w_host, dtype_host, rows_host, cols_host, ldw_host, bits, out_host, ldo_host, scale_host, zero_host, codes_host,
+                              (int)group, flags, stream);
+}
+
+int asvd_rtn_quant_grouped(const void* w, int dtype, int64_t rows, int64_t cols, int64_t ldw, int bits, void* out, int64_t ldo, float* scale,
+                           float* zero, void* codes, int* flag, void* stream, int64_t group) {
+    if (!rtn_args_ok(w, dtype, rows, cols, ldw, out, ldo) || !flag || bits < 1 || bits > 8) return ASVD_E_BADARG;
+    return asvd_rtn_quant_grouped_batched(1, &w, &dtype, &rows, &cols, &ldw, bits, &out, &ldo, &scale, &zero, &codes, flag, stream, group);
 }
 
 int asvd_rtn_quant(const void* w, int dtype, int64_t rows, int64_t cols, int64_t ldw, int bits, void* out, int64_t ldo, float* scale, float* zero,

@@ -25,6 +25,10 @@
 // loaded words with constant shifts (w8_code) and go through the same subtraction, product and conversion, chunk m to MFMA m, so
 // asvd_wb_linear_f16 gives the bits of asvd_w8_linear_f16 on the same codes.  asvd_wb_pack / asvd_wb_dequant write and read the format.
 //
+// K14, group-wise scales (GROUPED): scale / zero are [N, ng] with one pair per G = 64 or 128 codes of a row, ng = ceil(K / G).  The 64 codes a lane
+// owns in an iteration (k = 128 it + 64 g .. + 63) lie in ONE group, (128 it + 64 g) >> log2 G, so the lane loads one scale and one zero per
+// iteration, next to its code loads, and everything else is the loop above: the same tiles, the same k split, the same order of every sum.
+//
 // Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
 // with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
 #include "common.h"
@@ -40,6 +44,7 @@ constexpr int W8_WAVES = W8_THREADS / 64;
 constexpr int W8_KIT = 128;   // k values per iteration of a wave
 constexpr int W8_MAX_DEVICES = 64;   // devices whose CU count the host entry caches
 constexpr int W8_U = 2;       // iterations whose loads a wave issues before the first use
+constexpr int W8_ROW_SHIFT = 62;   // the "group shift" of per-row scales in the dequantization kernels
 
 // 32-bit words that hold a chunk of 16 codes of BITS bits, and with it 16-byte words that hold a lane's block of 64
 template <int BITS> constexpr int W8_CW = BITS / 2;
@@ -144,19 +149,24 @@ __device__ __forceinline__ f32x16 w8_iter_mfma(const uint4 (&cv)[W8_CW<BITS>], c
 }
 
 // BITS = 8: q holds one code per byte, ldq >= K.  BITS = 6, 4: q holds the bitstream rows (ldq bytes apart), K % 16 == 0 and everything is
-// 16-byte aligned (vec is 1)
-template <int BITS>
+// 16-byte aligned (vec is 1).  GROUPED: scale / zero are [N, ng], a group is 1 << gshift codes; K % 16 == 0 and vec is 1 at every width
+template <int BITS, bool GROUPED>
 __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
                                                               const float* __restrict__ scale, const float* __restrict__ zero,
                                                               const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ft,
-                                                              int nkfull /* whole iterations that take 16-byte loads */, int vec /* rows are 16-byte aligned */) {
+                                                              int nkfull /* whole iterations that take 16-byte loads */, int vec /* rows are 16-byte aligned */,
+                                                              int ng, int gshift) {
     __shared__ float red[W8_WAVES][16 * 64];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int i = lane & 31, g = lane >> 5;
     const int n0 = blockIdx.x * ft, t0 = blockIdx.y * 32;
     const int nvalid = min(ft, N - n0), tvalid = min(32, T - t0);
     const int wrow = n0 + min(i, nvalid - 1), xrow = t0 + min(i, tvalid - 1);
-    const float sc = scale[wrow], zr = zero[wrow];
+    float sc = 0.f, zr = 0.f;
+    if constexpr (!GROUPED) sc = scale[wrow], zr = zero[wrow];
+    // GROUPED: the row's scales and zeros; the lane's block of iteration `it` lies in group (W8_KIT it + 64 g) >> gshift
+    const float* srow = scale + (GROUPED ? (int64_t)wrow * ng : 0);
+    const float* zrow = zero + (GROUPED ? (int64_t)wrow * ng : 0);
     const uint8_t* qrow = q + (int64_t)wrow * ldq + 8 * BITS * g;   // the lane's 64-code block of iteration 0
     const uint16_t* xr = x + (int64_t)xrow * K + 64 * g;
     f32x16 acc;
@@ -168,14 +178,25 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
     int base = wave;
     for (; base + W8_WAVES * (W8_U - 1) < nkfull; base += W8_WAVES * W8_U) {
         uint4 cv[W8_U][W8_CW<BITS>], xv[W8_U][8];
+        float gs[W8_U], gz[W8_U];   // GROUPED: in flight with the code loads of the group (a whole iteration lies within K: the index is < ng)
 #pragma unroll
-        for (int u = 0; u < W8_U; ++u) w8_iter_load<BITS>(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
+        for (int u = 0; u < W8_U; ++u) {
+            w8_iter_load<BITS>(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
+            if constexpr (GROUPED) {
+                const int gi = ((base + W8_WAVES * u) * W8_KIT + 64 * g) >> gshift;
+                gs[u] = srow[gi], gz[u] = zrow[gi];
+            }
+        }
 #pragma unroll
-        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma<BITS>(cv[u], xv[u], sc, zr, acc);
+        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma<BITS>(cv[u], xv[u], GROUPED ? gs[u] : sc, GROUPED ? gz[u] : zr, acc);
     }
     for (; base < nkfull; base += W8_WAVES) {
         uint4 cv[W8_CW<BITS>], xv[8];
         w8_iter_load<BITS>(cv, xv, qrow, xr, base);
+        if constexpr (GROUPED) {
+            const int gi = (base * W8_KIT + 64 * g) >> gshift;
+            sc = srow[gi], zr = zrow[gi];
+        }
         acc = w8_iter_mfma<BITS>(cv, xv, sc, zr, acc);
     }
 
@@ -184,6 +205,12 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
     // (iteration `it` belongs to wave it % 4 on both paths, so the result does not depend on which path the alignment selects)
     for (int it = nkfull + ((wave - nkfull) & (W8_WAVES - 1)); it < nk; it += W8_WAVES) {
         uint4 cv[W8_CW<BITS>];
+        if constexpr (GROUPED) {
+            // the lane's four chunks lie in one group (G % 64 == 0).  A block that starts at or beyond K has no group: it reads the row's last
+            // pair, and its chunks are masked below
+            const int gi = min((it * W8_KIT + 64 * g) >> gshift, ng - 1);
+            sc = srow[gi], zr = zrow[gi];
+        }
         if (BITS != 8) {   // the lane's block as a whole (rows are padded to whole blocks); a block that starts at or beyond K is not there
 #pragma unroll
             for (int m = 0; m < W8_CW<BITS>; ++m)
@@ -239,16 +266,18 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
 }
 
 // ---- dequantization to a dense weight ---------------------------------------------------------------------------------------------
+// scale / zero are [rows, ng], a group is 1 << gshift columns (per row: ng = 1 and W8_ROW_SHIFT, which sends every column to group 0).  A
+// thread's 16 codes start at a multiple of 16 and so share one group
 // one thread per 16 consecutive codes of a row, 16-byte loads and stores (cols % 16 == 0, aligned rows)
 template <int DT>
 __global__ __launch_bounds__(W8_THREADS) void w8_dequant_kernel(const uint8_t* __restrict__ q, int64_t ldq, const float* __restrict__ scale,
                                                                const float* __restrict__ zero, int64_t rows, int64_t cols, void* __restrict__ out,
-                                                               int64_t ldo) {
+                                                               int64_t ldo, int64_t ng, int gshift) {
     const int64_t chunks = (cols + 15) / 16;
     const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
     if (id >= rows * chunks) return;
     const int64_t row = id / chunks, c0 = (id - row * chunks) * 16;
-    const float sc = scale[row], zr = zero[row];
+    const float sc = scale[row * ng + (c0 >> gshift)], zr = zero[row * ng + (c0 >> gshift)];
     const uint8_t* qp = q + row * ldq + c0;
     typename elem<DT>::T* op = (typename elem<DT>::T*)out + row * ldo + c0;
     {
@@ -279,11 +308,11 @@ __global__ __launch_bounds__(W8_THREADS) void w8_dequant_kernel(const uint8_t* _
 template <int DT>
 __global__ __launch_bounds__(W8_THREADS) void w8_dequant_elem_kernel(const uint8_t* __restrict__ q, int64_t ldq, const float* __restrict__ scale,
                                                                     const float* __restrict__ zero, int64_t rows, int64_t cols,
-                                                                    void* __restrict__ out, int64_t ldo) {
+                                                                    void* __restrict__ out, int64_t ldo, int64_t ng, int gshift) {
     const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
     if (id >= rows * cols) return;
-    const int64_t row = id / cols, c = id - row * cols;
-    elem<DT>::st(out, row * ldo + c, w8_value((uint32_t)q[row * ldq + c], scale[row], zero[row]));
+    const int64_t row = id / cols, c = id - row * cols, si = row * ng + (c >> gshift);
+    elem<DT>::st(out, row * ldo + c, w8_value((uint32_t)q[row * ldq + c], scale[si], zero[si]));
 }
 
 // ---- codes at their own width: pack and dequantization -----------------------------------------------------------------------------
@@ -320,12 +349,12 @@ __global__ __launch_bounds__(W8_THREADS) void wb_pack_kernel(const uint8_t* __re
 template <int DT, int BITS>
 __global__ __launch_bounds__(W8_THREADS) void wb_dequant_kernel(const uint8_t* __restrict__ q, int64_t ld_bytes, const float* __restrict__ scale,
                                                                const float* __restrict__ zero, int64_t rows, int64_t cols, void* __restrict__ out,
-                                                               int64_t ldo, int vec) {
+                                                               int64_t ldo, int vec, int64_t ng, int gshift) {
     const int64_t chunks = (cols + 15) / 16;
     const int64_t id = (int64_t)blockIdx.x * W8_THREADS + threadIdx.x;
     if (id >= rows * chunks) return;
     const int64_t row = id / chunks, c0 = (id - row * chunks) * 16;
-    const float sc = scale[row], zr = zero[row];
+    const float sc = scale[row * ng + (c0 >> gshift)], zr = zero[row * ng + (c0 >> gshift)];
     const uint32_t* qp = (const uint32_t*)(q + row * ld_bytes + c0 / 8 * BITS);
     uint32_t w[W8_CW<BITS>];
 #pragma unroll
@@ -379,17 +408,13 @@ int w8_feature_tile(int nT, int64_t N, int cus) {
     return ft;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t asvd_w8_linear_max_tokens(void) { return ASVD_W8_MAX_TOKENS; }
-
-int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias, int64_t N,
-                       int64_t K, void* y, void* stream) {
+// group: 0 (scale / zero [N]) or 64 / 128 (K14: [N, ceil(K / group)]); the entry points have checked it
+int w8_linear_launch(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int group, const void* bias,
+                     int64_t N, int64_t K, void* y, void* stream) {
     if (!x || !q || !scale || !zero || !y) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || ldq < K || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (group && (K % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16 || ldq % 16)) return ASVD_E_BADARG;   // grouped: 16-byte loads only
     int cus = 0;
     const int st = w8_cu_count(&cus);
     if (st != ASVD_OK) return st;
@@ -397,15 +422,22 @@ int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, con
     const int ft = w8_feature_tile(nT, N, cus);
     const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)q % 16 == 0) && (K % 8 == 0) && (ldq % 16 == 0);
     const int nkfull = vec ? (int)(K / W8_KIT) : 0;
-    hipLaunchKernelGGL(w8_linear_kernel<8>, dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
-                       (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
-                       nkfull, vec ? 1 : 0);
+    if (group)
+        hipLaunchKernelGGL((w8_linear_kernel<8, true>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                           (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
+                           nkfull, 1, (int)ceil_div64(K, group), group == 64 ? 6 : 7);
+    else
+        hipLaunchKernelGGL((w8_linear_kernel<8, false>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                           (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
+                           nkfull, vec ? 1 : 0, 1, 0);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
 }
 
-int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out, int out_dtype,
-                    int64_t ldo, void* stream) {
+int w8_dequant_launch(const void* q, int64_t ldq, const float* scale, const float* zero, int group, int64_t rows, int64_t cols, void* out,
+                      int out_dtype, int64_t ldo, void* stream) {
+    const int64_t ng = group ? ceil_div64(cols, group) : 1;
+    const int gshift = group == 64 ? 6 : group == 128 ? 7 : W8_ROW_SHIFT;
     if (!q || !scale || !zero || !out || rows < 1 || cols < 1 || ldq < cols || ldo < cols || !dtype_ok(out_dtype)) return ASVD_E_BADARG;
     const int64_t es = (int64_t)dtype_size(out_dtype);
     if ((uintptr_t)out % es) return ASVD_E_BADARG;
@@ -415,14 +447,95 @@ int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float*
     if (vec_ok) {
         ASVD_DISPATCH_DTYPE(out_dtype, DT,
                             hipLaunchKernelGGL(w8_dequant_kernel<DT>, dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint8_t*)q,
-                                               ldq, scale, zero, rows, cols, out, ldo));
+                                               ldq, scale, zero, rows, cols, out, ldo, ng, gshift));
     } else {
         ASVD_DISPATCH_DTYPE(out_dtype, DT,
                             hipLaunchKernelGGL(w8_dequant_elem_kernel<DT>, dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
-                                               (const uint8_t*)q, ldq, scale, zero, rows, cols, out, ldo));
+                                               (const uint8_t*)q, ldq, scale, zero, rows, cols, out, ldo, ng, gshift));
     }
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
+}
+
+int wb_dequant_launch(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int group, int64_t rows, int64_t cols,
+                      void* out, int out_dtype, int64_t ldo, void* stream) {
+    const int64_t ng = group ? ceil_div64(cols, group) : 1;
+    const int gshift = group == 64 ? 6 : group == 128 ? 7 : W8_ROW_SHIFT;
+    if (!q || !scale || !zero || !out || rows < 1 || cols < 1 || ldo < cols || !dtype_ok(out_dtype) || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
+    if (ld_bytes < wb_row_bytes(cols, bits) || (uintptr_t)q % 4 || ld_bytes % 4) return ASVD_E_BADARG;   // 4-byte loads
+    const int64_t es = (int64_t)dtype_size(out_dtype);
+    if ((uintptr_t)out % es) return ASVD_E_BADARG;
+    const int vec = (cols % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((ldo * es) % 16 == 0);
+    const int64_t grid = ceil_div64(rows * ((cols + 15) / 16), W8_THREADS);
+    if (grid > 0x7fffffff) return ASVD_E_BADARG;
+    if (bits == 6) {
+        ASVD_DISPATCH_DTYPE(out_dtype, DT,
+                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 6>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec, ng, gshift));
+    } else {
+        ASVD_DISPATCH_DTYPE(out_dtype, DT,
+                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 4>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
+                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec, ng, gshift));
+    }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+int wb_linear_launch(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int group,
+                     const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (!x || !q || !scale || !zero || !y || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
+    if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
+    if (ld_bytes < wb_row_bytes(K, bits) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    int cus = 0;
+    const int st = w8_cu_count(&cus);
+    if (st != ASVD_OK) return st;
+    const int nT = (int)((T + 31) / 32);
+    const int ft = w8_feature_tile(nT, N, cus);
+    const dim3 grid((unsigned)ceil_div64(N, ft), (unsigned)nT);
+    const int ng = group ? (int)ceil_div64(K, group) : 1, gshift = group == 64 ? 6 : 7;
+    if (group && bits == 6)
+        hipLaunchKernelGGL((w8_linear_kernel<6, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+                           ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, ng, gshift);
+    else if (group)
+        hipLaunchKernelGGL((w8_linear_kernel<4, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+                           ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, ng, gshift);
+    else if (bits == 6)
+        hipLaunchKernelGGL((w8_linear_kernel<6, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+                           ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, 1, 0);
+    else
+        hipLaunchKernelGGL((w8_linear_kernel<4, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+                           ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, 1, 0);
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t asvd_w8_linear_max_tokens(void) { return ASVD_W8_MAX_TOKENS; }
+
+int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias, int64_t N,
+                       int64_t K, void* y, void* stream) {
+    return w8_linear_launch(x, T, q, ldq, scale, zero, 0, bias, N, K, y, stream);
+}
+
+int asvd_w8_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group,
+                               const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (group != 64 && group != 128) return ASVD_E_BADARG;
+    return w8_linear_launch(x, T, q, ldq, scale, zero, (int)group, bias, N, K, y, stream);
+}
+
+int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out, int out_dtype,
+                    int64_t ldo, void* stream) {
+    return w8_dequant_launch(q, ldq, scale, zero, 0, rows, cols, out, out_dtype, ldo, stream);
+}
+
+int asvd_w8_dequant_grouped(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group, int64_t rows, int64_t cols, void* out,
+                            int out_dtype, int64_t ldo, void* stream) {
+    if (group != 64 && group != 128) return ASVD_E_BADARG;
+    return w8_dequant_launch(q, ldq, scale, zero, (int)group, rows, cols, out, out_dtype, ldo, stream);
 }
 
 int64_t asvd_wb_row_bytes(int64_t cols, int bits) { return (cols < 1 || (bits != 4 && bits != 6)) ? -1 : wb_row_bytes(cols, bits); }
@@ -444,46 +557,24 @@ int asvd_wb_pack(const void* q, int64_t ldq, int64_t rows, int64_t cols, int bit
 
 int asvd_wb_dequant(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out,
                     int out_dtype, int64_t ldo, void* stream) {
-    if (!q || !scale || !zero || !out || rows < 1 || cols < 1 || ldo < cols || !dtype_ok(out_dtype) || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
-    if (ld_bytes < wb_row_bytes(cols, bits) || (uintptr_t)q % 4 || ld_bytes % 4) return ASVD_E_BADARG;   // 4-byte loads
-    const int64_t es = (int64_t)dtype_size(out_dtype);
-    if ((uintptr_t)out % es) return ASVD_E_BADARG;
-    const int vec = (cols % 16 == 0) && ((uintptr_t)out % 16 == 0) && ((ldo * es) % 16 == 0);
-    const int64_t grid = ceil_div64(rows * ((cols + 15) / 16), W8_THREADS);
-    if (grid > 0x7fffffff) return ASVD_E_BADARG;
-    if (bits == 6) {
-        ASVD_DISPATCH_DTYPE(out_dtype, DT,
-                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 6>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
-                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec));
-    } else {
-        ASVD_DISPATCH_DTYPE(out_dtype, DT,
-                            hipLaunchKernelGGL((wb_dequant_kernel<DT, 4>), dim3((unsigned)grid), dim3(W8_THREADS), 0, (hipStream_t)stream,
-                                               (const uint8_t*)q, ld_bytes, scale, zero, rows, cols, out, ldo, vec));
-    }
-    ASVD_HIP_CHECK(hipGetLastError());
-    return ASVD_OK;
+    return wb_dequant_launch(q, ld_bytes, bits, scale, zero, 0, rows, cols, out, out_dtype, ldo, stream);
+}
+
+int asvd_wb_dequant_grouped(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group, int64_t rows,
+                            int64_t cols, void* out, int out_dtype, int64_t ldo, void* stream) {
+    if (group != 64 && group != 128) return ASVD_E_BADARG;
+    return wb_dequant_launch(q, ld_bytes, bits, scale, zero, (int)group, rows, cols, out, out_dtype, ldo, stream);
 }
 
 int asvd_wb_linear_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, const void* bias,
                        int64_t N, int64_t K, void* y, void* stream) {
-    if (!x || !q || !scale || !zero || !y || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
-    if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
-    if (ld_bytes < wb_row_bytes(K, bits) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
-    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
-    int cus = 0;
-    const int st = w8_cu_count(&cus);
-    if (st != ASVD_OK) return st;
-    const int nT = (int)((T + 31) / 32);
-    const int ft = w8_feature_tile(nT, N, cus);
-    const dim3 grid((unsigned)ceil_div64(N, ft), (unsigned)nT);
-    if (bits == 6)
-        hipLaunchKernelGGL(w8_linear_kernel<6>, grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q, ld_bytes,
-                           scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1);
-    else
-        hipLaunchKernelGGL(w8_linear_kernel<4>, grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q, ld_bytes,
-                           scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1);
-    ASVD_HIP_CHECK(hipGetLastError());
-    return ASVD_OK;
+    return wb_linear_launch(x, T, q, ld_bytes, bits, scale, zero, 0, bias, N, K, y, stream);
+}
+
+int asvd_wb_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                               int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (group != 64 && group != 128) return ASVD_E_BADARG;
+    return wb_linear_launch(x, T, q, ld_bytes, bits, scale, zero, (int)group, bias, N, K, y, stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@ A model whose weights were packed (`--weight_quant_storage packed`: W8Linear mod
 "storage": "uint8"}` in config.json and WITHOUT `auto_map` and the remote-code files, which cannot rebuild packed modules: such a repo loads
 with `load_asvd_repo` only.  A model whose codes are stored at their own width (`--weight_quant_storage bitpacked`: WBLinear modules) is written
 the same way with `<layer>.qbits` (uint8 bitstream rows, modules/wb_linear.py) in place of `.qweight` and `"storage": "bitstream64"`.  One
-model holds one width and one storage form.
+model holds one width and one storage form.  Group-wise scales (`--weight_quant_group_size G`) add `"group_size": G` to `weight_quant` and
+make `.scales` / `.zeros` [out, ceil(in / G)]; the key is absent for per-row scales, and one model holds one group size.
 """
 import json
 import os
@@ -24,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .modules.svd_linear import SVDLinear
-from .modules.w8_linear import W8Linear
+from .modules.w8_linear import W8Linear, param_shape
 from .modules.wb_linear import WBLinear, row_bytes
 
 _FAMILIES = {
@@ -118,7 +119,22 @@ def bitpacked_layers_of(model):
     return {name: int(m.bits) for name, m in model.named_modules() if isinstance(m, WBLinear)}
 
 
-def replace_with_bitpacked(model, state, bits, dtype=None):
+def group_sizes_of(model):
+    """the set of group sizes (0: per row) of the packed layers of the model"""
+    return {int(getattr(m, "group_size", 0)) for m in model.modules() if isinstance(m, (W8Linear, WBLinear))}
+
+
+def _check_param_shapes(state, full_name, out_f, in_f, group_size):
+    """the checkpoint's scales / zeros of a packed layer must have the shape the group size gives them"""
+    want = param_shape(out_f, in_f, group_size)
+    for key in ("scales", "zeros"):
+        have = state.get(f"{full_name}.{key}")
+        if have is not None and tuple(have.shape) != want:
+            raise ValueError(f"{full_name}.{key} is {tuple(have.shape)} in the checkpoint, but weight_quant.group_size={group_size} makes it "
+                             f"{want} for a [{out_f}, {in_f}] weight")
+
+
+def replace_with_bitpacked(model, state, bits, dtype=None, group_size=0):
     """Swap every module whose checkpoint keys end in `.qbits` for an empty WBLinear.  in_features comes from the module that is there (the base
     architecture's Linear, or the factor pair built from truncation_ranks); the checkpoint's rows must be the bitstream of that many codes."""
     for key in [k for k in state if k.endswith(".qbits")]:
@@ -128,12 +144,13 @@ def replace_with_bitpacked(model, state, bits, dtype=None):
         old = getattr(parent, child)
         if not isinstance(old, nn.Linear) or tuple(state[key].shape) != (old.out_features, row_bytes(old.in_features, bits)):
             raise ValueError(f"{full_name}: bit-packed weight {tuple(state[key].shape)} ({bits} bits) does not fit {old}")
+        _check_param_shapes(state, full_name, old.out_features, old.in_features, group_size)
         setattr(parent, child, WBLinear(old.in_features, old.out_features, bias=old.bias is not None, bits=bits, weight_dtype=dtype or old.weight.dtype,
-                                        device=old.weight.device))
+                                        device=old.weight.device, group_size=group_size))
     return model
 
 
-def replace_with_packed(model, state, bits=8, dtype=None):
+def replace_with_packed(model, state, bits=8, dtype=None, group_size=0):
     """Swap every module whose checkpoint keys end in `.qweight` for an empty W8Linear of the checkpoint's shape, so that the packed keys fit."""
     for key in [k for k in state if k.endswith(".qweight")]:
         full_name = key[: -len(".qweight")]
@@ -143,8 +160,9 @@ def replace_with_packed(model, state, bits=8, dtype=None):
         out_f, in_f = state[key].shape
         if not isinstance(old, nn.Linear) or (old.out_features, old.in_features) != (out_f, in_f):
             raise ValueError(f"{full_name}: packed weight {tuple(state[key].shape)} does not fit {old}")
+        _check_param_shapes(state, full_name, out_f, in_f, group_size)
         setattr(parent, child, W8Linear(in_f, out_f, bias=old.bias is not None, bits=bits, weight_dtype=dtype or old.weight.dtype,
-                                        device=old.weight.device))
+                                        device=old.weight.device, group_size=group_size))
     return model
 
 
@@ -169,7 +187,12 @@ def save_asvd_repo(model, save_path, tokenizer=None, family=None):
         packed = packed or bitpacked
         if len(set(packed.values())) != 1:
             raise ValueError(f"packed layers of several bit widths in one model: {sorted(set(packed.values()))}")
+        groups = group_sizes_of(model)
+        if len(groups) != 1:
+            raise ValueError(f"packed layers of several group sizes in one model: {sorted(groups)}")
         config["weight_quant"] = {"method": "rtn", "bits": next(iter(packed.values())), "storage": storage}
+        if next(iter(groups)):
+            config["weight_quant"]["group_size"] = next(iter(groups))
         config.pop("auto_map", None)
         with open(os.path.join(save_path, "config.json"), "w") as f:
             json.dump(config, f, indent=2)
@@ -234,11 +257,14 @@ def load_asvd_repo(path, dtype=torch.float16, device="cpu"):
         packed_dtype = raw.get("torch_dtype") or raw.get("dtype")
         if packed_dtype is not None and getattr(torch, str(packed_dtype), None) != dtype:
             raise ValueError(f"{path} holds weights packed from {packed_dtype}; load it with dtype=torch.{packed_dtype} (got {dtype})")
-        replace_with_packed(model, state, bits=int(wq.get("bits", 8)), dtype=dtype)
+        group_size = int(wq.get("group_size", 0))
+        if group_size not in (0, 64, 128):
+            raise ValueError(f"{path}: weight_quant.group_size must be 64 or 128 when present (got {group_size})")
+        replace_with_packed(model, state, bits=int(wq.get("bits", 8)), dtype=dtype, group_size=group_size)
         if any(k.endswith(".qbits") for k in state):
             if "bits" not in wq:
                 raise ValueError(f"{path} holds bit-packed weights but config.json does not give their width (weight_quant.bits)")
-            replace_with_bitpacked(model, state, bits=int(wq["bits"]), dtype=dtype)
+            replace_with_bitpacked(model, state, bits=int(wq["bits"]), dtype=dtype, group_size=group_size)
     missing, unexpected = model.load_state_dict(state, strict=False)
     tied_ok = {"lm_head.weight"} if getattr(cfg, "tie_word_embeddings", False) else set()
     bad_missing = [k for k in missing if k not in tied_ok and not k.endswith("rotary_emb.inv_freq")]

@@ -9,16 +9,21 @@ kernel that unpacks in registers and gives the bits of the W8A16 kernel on the s
 a temporary and calls F.linear on it.
 
 Neither an nn.Linear nor a W8Linear on purpose: the nn.Linear selections must keep ignoring packed layers and export.packed_layers_of must keep
-telling the two storage forms apart."""
+telling the two storage forms apart.
+
+Group-wise scales (`group_size` 64 or 128, K14): `scales` / `zeros` are [out, ceil(in / group_size)], one pair per group of that many input
+columns, as in W8Linear; `group_size` 0 is the per-row form above.  4 bits with groups of 128 is 4.5 bits per weight."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .packed_linear import PackedLinear
+from .w8_linear import expand_groups, param_shape
 
 # Token count up to which forward() takes the kernel.  NOT MEASURED for this kernel: the value is W8_FORWARD_MAX_TOKENS (modules/w8_linear.py),
 # whose tile loop this kernel shares; tools/bench_w8_forward.py --code_bits 6 / 4 (with and without --force_kernel) measures WBLinear's own two
-# paths.  The figures hold for rows that allow 16-byte loads only: see WBLinear.kernel_rows_ok.
+# paths.  The figures hold for rows that allow 16-byte loads only: see WBLinear.kernel_rows_ok.  Layers with group-wise scales take the same
+# constant, NOT MEASURED for grouped scales either (--group_size of the same tool).
 WB_FORWARD_MAX_TOKENS = 16
 
 WB_BITS = (4, 6)
@@ -60,24 +65,29 @@ class WBLinear(PackedLinear):
     they are what state_dict() and save_pretrained() write) and an optional `bias` buffer in the original dtype.  `in_features` is an attribute:
     the padded buffer does not tell it."""
 
-    def __init__(self, in_features, out_features, bias=True, bits=6, weight_dtype=torch.float16, device=None):
+    def __init__(self, in_features, out_features, bias=True, bits=6, weight_dtype=torch.float16, device=None, group_size=0):
         super().__init__()
         self.in_features, self.out_features, self.bits, self.weight_dtype = int(in_features), int(out_features), int(bits), weight_dtype
+        self.group_size = ops._group(group_size)
         nb = row_bytes(self.in_features, self.bits)
+        pshape = param_shape(self.out_features, self.in_features, self.group_size)
         self.register_buffer("qbits", torch.zeros((self.out_features, nb), dtype=torch.uint8, device=device))
-        self.register_buffer("scales", torch.zeros(self.out_features, dtype=torch.float32, device=device))
-        self.register_buffer("zeros", torch.zeros(self.out_features, dtype=torch.float32, device=device))
+        self.register_buffer("scales", torch.zeros(pshape, dtype=torch.float32, device=device))
+        self.register_buffer("zeros", torch.zeros(pshape, dtype=torch.float32, device=device))
         self.register_buffer("bias", torch.zeros(self.out_features, dtype=weight_dtype, device=device) if bias else None)
 
     @classmethod
-    def from_bits(cls, qbits, in_features, scales, zeros, bias, bits, weight_dtype):
+    def from_bits(cls, qbits, in_features, scales, zeros, bias, bits, weight_dtype, group_size=0):
         """wrap bitstream rows (ops.wb_pack) and the scale / zero of ops.rtn_quant_batched(..., want_params=True) without copying them"""
         if qbits.dim() != 2 or qbits.dtype != torch.uint8 or qbits.shape[1] != row_bytes(in_features, bits):
             raise ValueError(f"qbits {tuple(qbits.shape)} {qbits.dtype} is not the bitstream of {in_features} codes of {bits} bits per row")
         self = cls.__new__(cls)
         nn.Module.__init__(self)
         self.out_features, self.in_features = int(qbits.shape[0]), int(in_features)
-        self.bits, self.weight_dtype = int(bits), weight_dtype
+        self.bits, self.weight_dtype, self.group_size = int(bits), weight_dtype, ops._group(group_size)
+        pshape = param_shape(self.out_features, self.in_features, self.group_size)
+        if self.group_size and (tuple(scales.shape) != pshape or tuple(zeros.shape) != pshape):
+            raise ValueError(f"group_size={self.group_size}: scales / zeros must be {list(pshape)} (got {tuple(scales.shape)}, {tuple(zeros.shape)})")
         self.register_buffer("qbits", qbits)
         self.register_buffer("scales", scales)
         self.register_buffer("zeros", zeros)
@@ -85,11 +95,11 @@ class WBLinear(PackedLinear):
         return self
 
     @classmethod
-    def from_codes(cls, qweight, scales, zeros, bias, bits, weight_dtype):
+    def from_codes(cls, qweight, scales, zeros, bias, bits, weight_dtype, group_size=0):
         """from one-byte codes [out, in] (what W8Linear.from_codes wraps): packed on the device by csrc/w8_linear.hip, on the CPU in torch"""
         row_bytes(qweight.shape[1], bits)
         qbits = ops.wb_pack(qweight, bits) if qweight.is_cuda else pack_codes_torch(qweight, bits)
-        return cls.from_bits(qbits, qweight.shape[1], scales, zeros, bias, bits, weight_dtype)
+        return cls.from_bits(qbits, qweight.shape[1], scales, zeros, bias, bits, weight_dtype, group_size)
 
     def codes(self):
         """the codes one per byte, uint8 [out, in]"""
@@ -99,8 +109,9 @@ class WBLinear(PackedLinear):
         """the weight in weight_dtype.  CUDA: csrc/w8_linear.hip; CPU: a torch unpack, then W8Linear's arithmetic (fp32 subtraction, one fp32
         product, one rounding)"""
         if self.qbits.is_cuda:
-            return ops.wb_dequant(self.qbits, self.bits, self.in_features, self.scales, self.zeros, self.weight_dtype)
-        return (self.scales[:, None] * (self.codes().float() - self.zeros[:, None])).to(self.weight_dtype)
+            return ops.wb_dequant(self.qbits, self.bits, self.in_features, self.scales, self.zeros, self.weight_dtype, group_size=self.group_size)
+        sc, zr = (expand_groups(p, self.in_features, self.group_size) for p in (self.scales, self.zeros))
+        return (sc * (self.codes().float() - zr)).to(self.weight_dtype)
 
     def kernel_rows_ok(self):
         """the kernel takes whole 16-code chunks through 16-byte loads only: in_features % 16 == 0 and 16-byte-aligned contiguous storage (a row
@@ -111,9 +122,10 @@ class WBLinear(PackedLinear):
     def forward(self, x):
         x2d = self._kernel_input(x, WB_FORWARD_MAX_TOKENS)
         if x2d is not None:
-            y = ops.wb_linear(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias)
+            y = ops.wb_linear(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size)
             return y.view(*x.shape[:-1], self.out_features)
         return self._dense_forward(x)
 
     def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, bits={self.bits}, weight_dtype={self.weight_dtype}"
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, bits={self.bits}, weight_dtype={self.weight_dtype}" + (
+            f", group_size={self.group_size}" if self.group_size else "")

@@ -388,13 +388,44 @@ def reconstruct_err(W, A, B):
     return out
 
 
-def rtn_quant_batched(ws, bits, want_params=False):
+GROUP_SIZES = (64, 128)   # K14: columns per scale / zero pair; 0 stands for one pair per row
+
+
+def _group(group_size):
+    g = int(group_size)
+    if g != 0 and g not in GROUP_SIZES:
+        raise ValueError(f"group_size must be 0 (per row), 64 or 128 (got {group_size})")
+    return g
+
+
+def n_groups(cols, group_size):
+    """groups per row of `cols` columns: ceil(cols / group_size); the last one is shorter when cols is no multiple of it"""
+    return (int(cols) + group_size - 1) // group_size
+
+
+def _check_params(what, scale, zero, rows, cols, group, dev):
+    """scale / zero fp32 contiguous on `dev`: [rows] per row (any shape of that many elements, as before), [rows, ng] per group"""
+    ok = scale.dtype == torch.float32 and zero.dtype == torch.float32 and scale.is_contiguous() and zero.is_contiguous() \
+        and scale.device == dev and zero.device == dev
+    if group:
+        shape = (rows, n_groups(cols, group))
+        if not ok or tuple(scale.shape) != shape or tuple(zero.shape) != shape:
+            raise ValueError(f"{what} with group_size={group} needs scale / zero {list(shape)} fp32 contiguous on the device of the codes "
+                             f"(got {tuple(scale.shape)}, {tuple(zero.shape)})")
+    elif not ok or scale.numel() != rows or zero.numel() != rows:
+        raise ValueError(f"{what} needs scale / zero [{rows}] fp32 contiguous on the device of the codes")
+
+
+def rtn_quant_batched(ws, bits, want_params=False, group_size=0):
     """Round-to-nearest fake quantization (quantization.py:17-21,31-145 with perchannel=True, sym=False, mse=False) of a list of 2-D
     device tensors of any shapes, strides (unit column stride) and dtypes, ONE launch per 16 of them (asvd_rtn_quant_batched), then one
     host sync for the per-tensor flags.  Returns one entry per tensor: the quantized tensor (new, contiguous, same dtype) — or the input
     tensor itself when one of its rows has scale 0, which the reference leaves unchanged (Quantizer.ready()).  want_params: the entry is
-    (out, q, scale, zero, flagged) with q the uint8 codes [rows, cols] (0 where q is NaN) and scale / zero fp32 [rows]."""
+    (out, q, scale, zero, flagged) with q the uint8 codes [rows, cols] (0 where q is NaN) and scale / zero fp32 [rows].
+    group_size 64 / 128 (K14, asvd_rtn_quant_grouped_batched): every group of that many columns of a row is quantized as a row of its own;
+    scale / zero are [rows, ceil(cols / group_size)], and a tensor is flagged when one of its GROUPS has scale 0."""
     lib = L.load(True)
+    group = _group(group_size)
     if not 1 <= int(bits) <= 8:
         raise ValueError(f"bits must be in 1..8 (got {bits})")
     ws = list(ws)
@@ -411,16 +442,19 @@ def rtn_quant_batched(ws, bits, want_params=False):
     flags = torch.zeros(B, dtype=torch.int32, device=dev)
     if want_params:
         qs = [torch.empty(w.shape, dtype=torch.uint8, device=dev) for w in ws]
-        scales = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in ws]
-        zeros = [torch.empty(w.shape[0], dtype=torch.float32, device=dev) for w in ws]
+        pshape = (lambda w: (w.shape[0], n_groups(w.shape[1], group))) if group else (lambda w: (w.shape[0],))
+        scales = [torch.empty(pshape(w), dtype=torch.float32, device=dev) for w in ws]
+        zeros = [torch.empty(pshape(w), dtype=torch.float32, device=dev) for w in ws]
     vp, i64 = ctypes.c_void_p * B, ctypes.c_int64 * B
     ptrs = lambda ts: vp(*[t.data_ptr() for t in ts])  # noqa: E731
+    args = (B, ptrs(ws), (ctypes.c_int * B)(*[_dt(w) for w in ws]), i64(*[w.shape[0] for w in ws]), i64(*[w.shape[1] for w in ws]),
+            i64(*[w.stride(0) for w in ws]), int(bits), ptrs(outs), i64(*[w.shape[1] for w in ws]), ptrs(scales) if want_params else None,
+            ptrs(zeros) if want_params else None, ptrs(qs) if want_params else None, _ptr(flags), _stream(ws[0]))
     with _on(dev):
-        L.check(lib.asvd_rtn_quant_batched(B, ptrs(ws), (ctypes.c_int * B)(*[_dt(w) for w in ws]), i64(*[w.shape[0] for w in ws]),
-                                           i64(*[w.shape[1] for w in ws]), i64(*[w.stride(0) for w in ws]), int(bits), ptrs(outs),
-                                           i64(*[w.shape[1] for w in ws]), ptrs(scales) if want_params else None,
-                                           ptrs(zeros) if want_params else None, ptrs(qs) if want_params else None, _ptr(flags),
-                                           _stream(ws[0])), "asvd_rtn_quant_batched")
+        if group:
+            L.check(lib.asvd_rtn_quant_grouped_batched(*args, group), "asvd_rtn_quant_grouped_batched")
+        else:
+            L.check(lib.asvd_rtn_quant_batched(*args), "asvd_rtn_quant_batched")
     flagged = [bool(f) for f in flags.tolist()]
     res = [w if f else o for w, o, f in zip(ws, outs, flagged)]
     if want_params:
@@ -428,18 +462,20 @@ def rtn_quant_batched(ws, bits, want_params=False):
     return res
 
 
-def rtn_quant(w, bits, want_params=False):
+def rtn_quant(w, bits, want_params=False, group_size=0):
     """rtn_quant_batched for one tensor"""
-    return rtn_quant_batched([w], bits, want_params)[0]
+    return rtn_quant_batched([w], bits, want_params, group_size)[0]
 
 
 W8_MAX_TOKENS = 256  # ASVD_W8_MAX_TOKENS (asvd_w8_linear_max_tokens)
 
 
-def w8_linear(x2d, q, scale, zero, bias=None):
+def w8_linear(x2d, q, scale, zero, bias=None, group_size=0):
     """y = fp16(x2d . w^T + bias) with w = fp16(scale * (q - zero)) dequantized in registers (K12, asvd_w8_linear_f16): x2d [T <= 256, K] fp16
-    contiguous, q [N, K] uint8 (unit column stride), scale / zero [N] fp32, bias [N] fp16 or None.  One launch, deterministic."""
+    contiguous, q [N, K] uint8 (unit column stride), scale / zero [N] fp32, bias [N] fp16 or None.  One launch, deterministic.
+    group_size 64 / 128 (K14, asvd_w8_linear_grouped_f16): scale / zero [N, ceil(K / group_size)]; K % 16 == 0 and 16-byte-aligned x and rows only."""
     lib = L.load(True)
+    group = _group(group_size)
     _dev(x2d, "x")
     if x2d.dim() != 2 or q.dim() != 2 or x2d.dtype != torch.float16 or q.dtype != torch.uint8 or not x2d.is_contiguous() or q.stride(1) != 1:
         raise ValueError(f"w8_linear needs x [T, K] fp16 contiguous and q [N, K] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, {tuple(q.shape)} {q.dtype})")
@@ -447,27 +483,41 @@ def w8_linear(x2d, q, scale, zero, bias=None):
     N = q.shape[0]
     if q.shape[1] != K or not 1 <= T <= W8_MAX_TOKENS:
         raise ValueError(f"w8_linear: x {tuple(x2d.shape)} against q {tuple(q.shape)}; 1 <= tokens <= {W8_MAX_TOKENS}")
-    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != N or zero.numel() != N or not scale.is_contiguous() \
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or (not group and (scale.numel() != N or zero.numel() != N)) \
+            or not scale.is_contiguous() \
             or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
         raise ValueError("w8_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
     if q.device != x2d.device or scale.device != x2d.device or zero.device != x2d.device or (bias is not None and bias.device != x2d.device):
         raise ValueError("w8_linear: all tensors must live on the device of x")
+    if group:
+        _check_params("w8_linear", scale, zero, N, K, group, x2d.device)
+        if K % 16 or x2d.data_ptr() % 16 or q.data_ptr() % 16 or q.stride(0) % 16:
+            raise ValueError("w8_linear with group_size needs K % 16 == 0 and x and the rows of q 16-byte aligned")
     y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
     with _on(x2d.device):
+        if group:
+            L.check(lib.asvd_w8_linear_grouped_f16(x2d.data_ptr(), T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), group,
+                                                   bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)),
+                    "asvd_w8_linear_grouped_f16")
+            return y
         L.check(lib.asvd_w8_linear_f16(x2d.data_ptr(), T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(),
                                        bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_w8_linear_f16")
     return y
 
 
-def w8_dequant(q, scale, zero, dtype, out=None):
+def w8_dequant(q, scale, zero, dtype, out=None, group_size=0):
     """the dense weight scale * (q - zero) in `dtype` (fp16 / bf16 / fp32), value for value the `out` of rtn_quant for these codes
-    (asvd_w8_dequant).  q [rows, cols] uint8 with unit column stride; out: optional destination [rows, cols] with unit column stride."""
+    (asvd_w8_dequant).  q [rows, cols] uint8 with unit column stride; out: optional destination [rows, cols] with unit column stride.
+    group_size 64 / 128 (asvd_w8_dequant_grouped): scale / zero [rows, ceil(cols / group_size)]."""
     lib = L.load(True)
+    group = _group(group_size)
     _dev(q, "q")
     if q.dim() != 2 or q.dtype != torch.uint8 or q.stride(1) != 1 or dtype not in _DT:
         raise ValueError(f"w8_dequant needs q [rows, cols] uint8 with unit column stride and a float dtype (got {tuple(q.shape)} {q.dtype}, {dtype})")
     rows, cols = q.shape
-    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
+    if group:
+        _check_params("w8_dequant", scale, zero, rows, cols, group, q.device)
+    elif scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
             or not zero.is_contiguous() or scale.device != q.device or zero.device != q.device:
         raise ValueError("w8_dequant needs scale / zero [rows] fp32 contiguous on the device of q")
     if out is None:
@@ -477,6 +527,10 @@ def w8_dequant(q, scale, zero, dtype, out=None):
     if rows == 0 or cols == 0:
         return out
     with _on(q.device):
+        if group:
+            L.check(lib.asvd_w8_dequant_grouped(q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), group, rows, cols, out.data_ptr(),
+                                                _DT[dtype], out.stride(0), _stream(q)), "asvd_w8_dequant_grouped")
+            return out
         L.check(lib.asvd_w8_dequant(q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), rows, cols, out.data_ptr(), _DT[dtype],
                                     out.stride(0), _stream(q)), "asvd_w8_dequant")
     return out
@@ -508,10 +562,12 @@ def wb_pack(q, bits, out=None):
     return out
 
 
-def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None):
+def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None, group_size=0):
     """the dense weight scale * (code - zero) [rows, cols] in `dtype` (fp16 / bf16 / fp32) from bitstream rows qbits [rows, wb_row_bytes(cols,
-    bits)] (asvd_wb_dequant): value for value w8_dequant on the unpacked codes.  out: optional destination with unit column stride."""
+    bits)] (asvd_wb_dequant): value for value w8_dequant on the unpacked codes.  out: optional destination with unit column stride.
+    group_size 64 / 128 (asvd_wb_dequant_grouped): scale / zero [rows, ceil(cols / group_size)]."""
     lib = L.load(True)
+    group = _group(group_size)
     _dev(qbits, "qbits")
     if qbits.dim() != 2 or qbits.dtype != torch.uint8 or qbits.stride(1) != 1 or dtype not in _DT:
         raise ValueError(f"wb_dequant needs qbits [rows, row bytes] uint8 with unit column stride and a float dtype (got {tuple(qbits.shape)} "
@@ -519,7 +575,9 @@ def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None):
     rows, cols = qbits.shape[0], int(cols)
     if qbits.shape[1] != wb_row_bytes(cols, bits):
         raise ValueError(f"wb_dequant: {tuple(qbits.shape)} is not the bitstream of [{rows}, {cols}] codes of {bits} bits")
-    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
+    if group:
+        _check_params("wb_dequant", scale, zero, rows, cols, group, qbits.device)
+    elif scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != rows or zero.numel() != rows or not scale.is_contiguous() \
             or not zero.is_contiguous() or scale.device != qbits.device or zero.device != qbits.device:
         raise ValueError("wb_dequant needs scale / zero [rows] fp32 contiguous on the device of qbits")
     if out is None:
@@ -529,15 +587,21 @@ def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None):
     if rows == 0:
         return out
     with _on(qbits.device):
+        if group:
+            L.check(lib.asvd_wb_dequant_grouped(qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(), group, rows, cols,
+                                                out.data_ptr(), _DT[dtype], out.stride(0), _stream(qbits)), "asvd_wb_dequant_grouped")
+            return out
         L.check(lib.asvd_wb_dequant(qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(), rows, cols, out.data_ptr(),
                                     _DT[dtype], out.stride(0), _stream(qbits)), "asvd_wb_dequant")
     return out
 
 
-def wb_linear(x2d, qbits, bits, scale, zero, bias=None):
+def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0):
     """w8_linear on bitstream rows (K13, asvd_wb_linear_f16): x2d [T <= 256, K] fp16 contiguous, K % 16 == 0, qbits [N, wb_row_bytes(K, bits)]
-    uint8, scale / zero [N] fp32, bias [N] fp16 or None; x2d and the rows 16-byte aligned.  The bits of w8_linear on the same codes."""
+    uint8, scale / zero [N] fp32, bias [N] fp16 or None; x2d and the rows 16-byte aligned.  The bits of w8_linear on the same codes.
+    group_size 64 / 128 (K14, asvd_wb_linear_grouped_f16): scale / zero [N, ceil(K / group_size)]."""
     lib = L.load(True)
+    group = _group(group_size)
     _dev(x2d, "x")
     if x2d.dim() != 2 or qbits.dim() != 2 or x2d.dtype != torch.float16 or qbits.dtype != torch.uint8 or not x2d.is_contiguous() or qbits.stride(1) != 1:
         raise ValueError(f"wb_linear needs x [T, K] fp16 contiguous and qbits [N, row bytes] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, "
@@ -546,15 +610,23 @@ def wb_linear(x2d, qbits, bits, scale, zero, bias=None):
     N = qbits.shape[0]
     if K < 1 or K % 16 or qbits.shape[1] != wb_row_bytes(K, bits) or not 1 <= T <= W8_MAX_TOKENS:
         raise ValueError(f"wb_linear: x {tuple(x2d.shape)} against qbits {tuple(qbits.shape)} of {bits}-bit codes; K % 16 == 0, 1 <= tokens <= {W8_MAX_TOKENS}")
-    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or scale.numel() != N or zero.numel() != N or not scale.is_contiguous() \
+    if scale.dtype != torch.float32 or zero.dtype != torch.float32 or (not group and (scale.numel() != N or zero.numel() != N)) \
+            or not scale.is_contiguous() \
             or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
         raise ValueError("wb_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
+    if group:
+        _check_params("wb_linear", scale, zero, N, K, group, scale.device)
     if qbits.device != x2d.device or scale.device != x2d.device or zero.device != x2d.device or (bias is not None and bias.device != x2d.device):
         raise ValueError("wb_linear: all tensors must live on the device of x")
     if x2d.data_ptr() % 16 or qbits.data_ptr() % 16 or qbits.stride(0) % 16:
         raise ValueError("wb_linear needs x and the rows of qbits 16-byte aligned")
     y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
     with _on(x2d.device):
+        if group:
+            L.check(lib.asvd_wb_linear_grouped_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
+                                                   group, bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)),
+                    "asvd_wb_linear_grouped_f16")
+            return y
         L.check(lib.asvd_wb_linear_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
                                        bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_wb_linear_f16")
     return y

@@ -334,6 +334,36 @@ int asvd_wb_linear_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes
                        const void* bias, int64_t N, int64_t K, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K14  Group-wise RTN: one scale and one zero per group of G = 64 or 128 consecutive columns of a row instead of per row.  A row of K columns
+ *   has ng = ceil(K / G) groups; the last one holds K - (ng - 1) G columns when K is no multiple of G.  Group j of row n is quantized exactly as
+ *   K11 quantizes the one-row tensor W[n, jG : (j+1)G] (min / max including 0, -1 / +1 for an all-zero group, fp32 division, round half to even,
+ *   NaN-propagating min / max: a NaN poisons its own group only).  scale, zero: device float [rows, ng], row-major, contiguous.
+ *   `group` must be 64 or 128 in every entry below (per-row scales are the K11 - K13 entries); anything else returns ASVD_E_BADARG.
+ * asvd_rtn_quant_grouped, asvd_rtn_quant_grouped_batched:  asvd_rtn_quant / asvd_rtn_quant_batched with `group` as last argument.  The flag is
+ *   OR-ed with 1 when some GROUP's scale is 0 (the reference's Quantizer.ready() over the tensor reshaped to groups); such groups are copied.
+ * asvd_w8_linear_grouped_f16, asvd_wb_linear_grouped_f16:  the forwards of K12 / K13 with w[n, k] = fp16(scale[n, k / G] * (code - zero[n, k / G])),
+ *   formed in registers before the matrix instruction as there; the same tiles, k split and order of sums, so with every group of a row given
+ *   one scale and zero the result has the bits of the per-row entry, and the 6- and 4-bit forms give the bits of the 8-bit form on the same
+ *   codes.  At all three widths: K % 16 == 0, x and q 16-byte aligned, the leading dimension a multiple of 16.
+ * asvd_w8_dequant_grouped, asvd_wb_dequant_grouped:  the dense weight, bit for bit the `out` of the grouped quantizer; arguments as their
+ *   per-row siblings.
+ * Bad arguments return ASVD_E_BADARG before any device call. */
+int asvd_rtn_quant_grouped(const void* w, int dtype, int64_t rows, int64_t cols, int64_t ldw, int bits, void* out, int64_t ldo, float* scale,
+                           float* zero, void* codes, int* flag, void* stream, int64_t group);
+int asvd_rtn_quant_grouped_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host,
+                                   const int64_t* cols_host, const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host,
+                                   float* const* scale_host, float* const* zero_host, void* const* codes_host, int* flags, void* stream,
+                                   int64_t group);
+int asvd_w8_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group,
+                               const void* bias, int64_t N, int64_t K, void* y, void* stream);
+int asvd_w8_dequant_grouped(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group, int64_t rows, int64_t cols,
+                            void* out, int out_dtype, int64_t ldo, void* stream);
+int asvd_wb_dequant_grouped(const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group, int64_t rows,
+                            int64_t cols, void* out, int out_dtype, int64_t ldo, void* stream);
+int asvd_wb_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                               int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

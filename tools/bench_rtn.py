@@ -7,7 +7,9 @@ Per shape set: kernel time (device events around the 32 per-block batched launch
 algorithmic bytes (one read + one write of every weight: 2 x elements x 2 B), GB/s and the fraction of the 8 TB/s HBM spec over kernel time,
 the same step through asvd4llm_amd.quantization's per-block path (with its flag read-back), and the reference's torch sequence
 (quantization.py:17-21,31-145 restated op for op in torch: .float(), row min / max, scale, zero, round, clamp, dequantize, cast back) timed
-on the same GPU, with every output compared bit for bit."""
+on the same GPU, with every output compared bit for bit.
+--group_size 64 | 128 times the group-wise form (asvd_rtn_quant_grouped_batched: one scale and zero per group of that many columns) against the
+same torch sequence applied to the weight reshaped to groups (the whole groups as [rows * n, G], what is left of every row as [rows, rest])."""
 import argparse
 import ctypes
 import json
@@ -59,6 +61,18 @@ def torch_sequence(w, bits):
     return (scale * (q - zero)).to(w.dtype)
 
 
+@torch.no_grad()
+def torch_sequence_grouped(w, bits, group):
+    """torch_sequence on the weight reshaped to groups; unchanged when any group's scale is 0"""
+    rows, cols = w.shape
+    whole = cols // group * group
+    srcs = ([w[:, :whole].reshape(-1, group)] if whole else []) + ([w[:, whole:].contiguous()] if cols > whole else [])
+    parts = [torch_sequence(a, bits) for a in srcs]
+    if any(p is a for p, a in zip(parts, srcs)):   # torch_sequence returns its input when a scale is 0
+        return w
+    return torch.cat([p.reshape(rows, -1) for p in parts], dim=1)
+
+
 def bits_equal(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16))
 
@@ -68,7 +82,7 @@ def median(xs):
     return s[len(s) // 2]
 
 
-def run_set(blocks, bits, iters, warmup, dev, seed):
+def run_set(blocks, bits, iters, warmup, dev, seed, group=0):
     lib = L.load(True)
     g = torch.Generator(device=dev).manual_seed(seed)
     ws = [[(torch.randn(m, n, generator=g, device=dev, dtype=torch.float32) * 0.02).half() for m, n in blk] for blk in blocks]
@@ -85,7 +99,12 @@ def run_set(blocks, bits, iters, warmup, dev, seed):
 
     def launch_all():
         for c in calls:
-            L.check(lib.asvd_rtn_quant_batched(*c), "asvd_rtn_quant_batched")
+            if group:
+                L.check(lib.asvd_rtn_quant_grouped_batched(*c, group), "asvd_rtn_quant_grouped_batched")
+            else:
+                L.check(lib.asvd_rtn_quant_batched(*c), "asvd_rtn_quant_batched")
+
+    reference = (lambda w: torch_sequence_grouped(w, bits, group)) if group else (lambda w: torch_sequence(w, bits))
 
     def timed(fn, n):
         ts = []
@@ -104,12 +123,12 @@ def run_set(blocks, bits, iters, warmup, dev, seed):
 
     def ops_path():
         for blk in ws:
-            ops.rtn_quant_batched(blk, bits)
+            ops.rtn_quant_batched(blk, bits, group_size=group)
     timed(ops_path, max(1, warmup // 2))
     ops_ms = timed(ops_path, iters)
 
     def ref_path():
-        return [[torch_sequence(w, bits) for w in blk] for blk in ws]
+        return [[reference(w) for w in blk] for blk in ws]
     timed(ref_path, 1)
     ref_ms = timed(ref_path, max(1, iters // 2))
 
@@ -117,7 +136,7 @@ def run_set(blocks, bits, iters, warmup, dev, seed):
     for blk, oblk in zip(ws, outs):
         for w, o in zip(blk, oblk):
             compared += 1
-            mismatched += not bits_equal(o, torch_sequence(w, bits))
+            mismatched += not bits_equal(o, reference(w))
     elems = sum(w.numel() for blk in ws for w in blk)
     nbytes = 2 * elems * 2
     k = median(kern)
@@ -131,6 +150,7 @@ def run_set(blocks, bits, iters, warmup, dev, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bits", type=int, default=8)
+    ap.add_argument("--group_size", type=int, default=0, choices=[0, 64, 128], help="64 / 128: the group-wise quantizer (K14)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=233)
@@ -138,8 +158,10 @@ def main():
     dev = torch.device("cuda", 0)
     L.load(require_device=True)
     res = {"metric": "rtn_quant_kernel", "bits": args.bits, "dtype": "float16", "hbm_spec_Bps": HBM_SPEC, "sets": {}}
+    if args.group_size:
+        res["group_size"] = args.group_size
     for name, blocks in shape_sets().items():
-        res["sets"][name] = run_set(blocks, args.bits, args.iters, args.warmup, dev, args.seed)
+        res["sets"][name] = run_set(blocks, args.bits, args.iters, args.warmup, dev, args.seed, args.group_size)
         torch.cuda.empty_cache()
     res["bit_exact_vs_torch"] = all(s["bit_exact_vs_torch"] for s in res["sets"].values())
     print(json.dumps(res), flush=True)

@@ -15,7 +15,12 @@ between the outputs of (a) and (b) over all layers, relative to the largest outp
 --code_bits 6 | 4 quantizes to that width and adds
   (c) WBLinear modules holding the same codes at their own width (--weight_quant_storage bitpacked; csrc/w8_linear.hip, K13),
 timed in the same alternation and reported under "bitpacked" with the columns of (b), plus its time over (b)'s and whether it is slower than
-(b) by more than (b)'s own spread.  Without --code_bits the output is what it was."""
+(b) by more than (b)'s own spread.  Without --code_bits the output is what it was.
+--group_size 64 | 128 adds
+  (d) the modules of the narrowest path above ((c) with --code_bits 6 | 4, else (b)) on the SAME code buffers with group-wise scales and zeros
+      (csrc/w8_linear.hip, K14; every group of a row carries the row's pair, so (d) stands for the same weights and must give that path's bits),
+timed in the same alternation and reported under "grouped": its time over the per-row pass of the same width, the share of weight-side bytes the
+[N, ng] parameters add (8 / (G bits / 8) per code byte) and whether the slowdown stays within that share plus the per-row pass's own spread."""
 import argparse
 import json
 import os
@@ -35,7 +40,7 @@ from bench_rtn import HBM_SPEC, median, shape_sets  # noqa: E402
 TOKENS = (1, 4, 16, 64)
 
 
-def build_set(blocks, factored, bits, dev, seed, bitpacked=False):
+def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0):
     """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear[, WBLinear]) stages applied in order (BLinear, ALinear for a
     factored layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
     g = torch.Generator(device=dev).manual_seed(seed)
@@ -51,6 +56,11 @@ def build_set(blocks, factored, bits, dev, seed, bitpacked=False):
             stage = (lin, W.W8Linear.from_codes(q, scale, zero, None, bits, torch.float16))
             if bitpacked:
                 stage += (WB.WBLinear.from_codes(q, scale, zero, None, bits, torch.float16),)
+            if group:   # the per-row pair of every row, once per group: the same weights on the same code buffer
+                ng = ops.n_groups(q.shape[1], group)
+                gs, gz = scale[:, None].expand(-1, ng).contiguous(), zero[:, None].expand(-1, ng).contiguous()
+                stage += ((WB.WBLinear.from_bits(stage[2].qbits, q.shape[1], gs, gz, None, bits, torch.float16, group_size=group),) if bitpacked
+                          else (W.W8Linear.from_codes(q, gs, gz, None, bits, torch.float16, group_size=group),))
             stages.append(stage)
         out.append([[stages[i + 1], stages[i]] for i in range(0, len(stages), 2)] if factored else [[s] for s in stages])
     return out
@@ -109,7 +119,9 @@ def stats(ts):
 
 def run_set(blocks, factored, args, dev):
     bitpacked = args.code_bits != 8
-    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked)
+    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size)
+    base_path = 2 if bitpacked else 1                       # the per-row pass (d) is compared with
+    npaths = 2 + bitpacked + bool(args.group_size)
     stages = [s for blk in layers for layer in blk for s in layer]
     code_bytes = sum(s[1].qweight.numel() + 8 * s[1].out_features for s in stages)
     fp16_bytes = sum(2 * s[0].weight.numel() for s in stages)
@@ -117,6 +129,10 @@ def run_set(blocks, factored, args, dev):
     if bitpacked:
         bit_bytes = sum(s[2].qbits.numel() + 8 * s[2].out_features for s in stages)
         res["bitpacked_weight_bytes"] = bit_bytes
+    if args.group_size:
+        base_bytes = bit_bytes if bitpacked else code_bytes
+        grp_bytes = sum(s[-1].scales.numel() * 8 - 8 * s[-1].out_features for s in stages) + base_bytes
+        res.update({"grouped_weight_bytes": grp_bytes, "grouped_extra_byte_share": round(grp_bytes / base_bytes - 1, 4)})
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
     for T in args.tokens:
         xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
@@ -130,7 +146,7 @@ def run_set(blocks, factored, args, dev):
             rec.update({"bitpacked_kernel_dispatched": T <= WB.WB_FORWARD_MAX_TOKENS, "bitpacked_bytes": bit_bytes + act_bytes,
                         "bitpacked_max_abs_diff": diff_c, "bitpacked_max_rel_diff": diff_c / top if top else 0.0})
         for mode in ("eager", "graph"):
-            times = timed_paths(layers, xs, args.iters, args.warmup, mode == "graph", 3 if bitpacked else 2)
+            times = timed_paths(layers, xs, args.iters, args.warmup, mode == "graph", npaths)
             a, b = stats(times[0]), stats(times[1])
             rec[mode] = {"fp16_linear": a, "packed": b, "packed_over_fp16": round(b["median_ms"] / a["median_ms"], 4),
                          "packed_not_slower": b["median_ms"] <= a["median_ms"] + a["spread_ms"],
@@ -145,6 +161,18 @@ def run_set(blocks, factored, args, dev):
                                   "bitpacked_not_slower_than_packed": c["median_ms"] <= b["median_ms"] + b["spread_ms"],
                                   "bitpacked_gbps": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / 1e9, 1),
                                   "bitpacked_frac_of_hbm_spec": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / HBM_SPEC, 4)})
+            if args.group_size:   # against the per-row pass of the same width on the same codes; that pass's spread is the noise floor
+                base, d = stats(times[base_path]), stats(times[-1])
+                share = grp_bytes / base_bytes - 1
+                rec[mode].update({"grouped": d, "grouped_over_per_row": round(d["median_ms"] / base["median_ms"], 4),
+                                  "grouped_minus_per_row_ms": round(d["median_ms"] - base["median_ms"], 4),
+                                  "grouped_within_byte_share_plus_spread": d["median_ms"] <= base["median_ms"] * (1 + share) + base["spread_ms"],
+                                  "grouped_gbps": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / 1e9, 1),
+                                  "grouped_frac_of_hbm_spec": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / HBM_SPEC, 4)})
+        if args.group_size:
+            diff_d, _ = max_difference(layers, xs, npaths - 1)
+            same_bits = all(torch.equal(run_pass([[layer]], xs, npaths - 1), run_pass([[layer]], xs, base_path)) for layer in layers[0])
+            rec.update({"grouped_max_rel_diff": diff_d / top if top else 0.0, "grouped_bits_equal_per_row_block0": same_bits})
         res["tokens"][str(T)] = rec
     return res
 
@@ -154,6 +182,8 @@ def main():
     ap.add_argument("--bits", type=int, default=8)
     ap.add_argument("--code_bits", type=int, default=8, choices=[8, 6, 4],
                     help="6 / 4: quantize to that width (overrides --bits) and add path (c), WBLinear on the codes stored at their own width")
+    ap.add_argument("--group_size", type=int, default=0, choices=[0, 64, 128],
+                    help="64 / 128: add path (d), the narrowest packed path on the same codes with group-wise scales and zeros")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=233)
@@ -167,6 +197,8 @@ def main():
         args.bits = args.code_bits
         if args.force_kernel and args.rank_align % 16:
             ap.error("--force_kernel with --code_bits 6 / 4 needs --rank_align to be a multiple of 16: the bit-packed kernel takes K % 16 == 0 only")
+    if args.group_size and args.force_kernel and args.rank_align % 16:
+        ap.error("--force_kernel with --group_size needs --rank_align to be a multiple of 16: the grouped kernels take K % 16 == 0 only")
     L.load(require_device=True)
     dev = torch.device("cuda", 0)
     if args.force_kernel:
@@ -175,6 +207,8 @@ def main():
         WB.WB_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
     res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
            "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
+    if args.group_size:
+        res["group_size"] = args.group_size
     if args.code_bits != 8:
         res.update({"code_bits": args.code_bits, "bitpacked_dispatch_max_tokens": WB.WB_FORWARD_MAX_TOKENS})
     for name, blocks in shape_sets(0.9, args.rank_align).items():
