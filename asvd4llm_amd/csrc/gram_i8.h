@@ -96,7 +96,7 @@ __global__ __launch_bounds__(512) void gram_i8_kernel(const signed char* __restr
                                                       const int* __restrict__ ex, double* __restrict__ G, int64_t ldg, int64_t g_batch_stride,
                                                       int accumulate, int nt, const double* __restrict__ dp /* nullable: G_ij / (dp_i dp_j) is stored;
                                                       a column with dp = 0 gets a unit diagonal and zeros */) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // 2 x GI_STAGE_BYTES
+    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // GI_LDS_BYTES
     int Ib, Jb;
     gi_tri_block(nt, Ib, Jb);
     const int b = blockIdx.y;

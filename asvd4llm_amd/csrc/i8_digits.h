@@ -72,30 +72,90 @@ __device__ __forceinline__ void gi_tri_block(int nt, int& Ib, int& Jb) {
 // 4 Jb + (w & 3)), exactly, for wave w of a workgroup of 512 threads = one 128 x 128 block (64 x 32 per wave: 2 tiles x NW weights x 16
 // accumulator registers, two waves per SIMD).  A plane set is [digit a][panel P][16-index group kg][column c][16 bytes = reduction indices] with
 // `stride` bytes per digit: one (P, kg) piece of a digit is 512 contiguous bytes, and two consecutive pieces are the A (or B) operand of one
-// v_mfma_i32_32x32x32_i8 of a wave: lane l = 32 (kg & 1) + c reads its 16 bytes at offset 16 l.  Panels >= npA / npB read as zero.  A stage = 64
-// reduction indices (kgs is a multiple of 4) of the four A panels and the four B panels, three digits each: 2 x 24 KB through LDS in the planes'
-// own order (linear 16-byte pieces: no bank conflicts either way), double buffered in lds[2 x GI_STAGE_BYTES]; per stage and wave 2 x 18 (NW = 5:
-// all nine digit products) or 2 x 16 (NW = 4: the product of the two lowest digits dropped) matrix instructions on 2 x 9 operand reads.
+// v_mfma_i32_32x32x32_i8 of a wave: lane l = 32 (kg & 1) + c reads its 16 bytes at offset 16 l.
+// Panels >= npA / npB read as the LAST existing panel (npA, npB >= 1): the accumulators of such a panel hold products of real digits that belong
+// nowhere, and every caller drops them — gram_i8_kernel and fullcheck_i8_kernel by `if (J >= nb) return` / `if (I > J || I >= nb) continue`,
+// nn_gemm_i8_kernel by `if (j >= k) return` (k <= 32 jps); on its A side it tests rows only against the matrix, so launch_nn_i8 gives it segments
+// of a multiple of four panels (checked there), which hold no clamped panel.  A caller
+// that stores a block of a panel >= np must zero it itself.
+// A stage = 64 reduction indices (kgs is a multiple of 4) of the four A panels and the four B panels, three digits each: 2 x 24 KB in LDS in the
+// planes' own order (linear 16-byte pieces: no bank conflicts either way).  The stages go through a ring of GI_SLOTS = 3 slots filled by
+// global_load_lds_dwordx4 (six per thread and stage, 1 KiB contiguous per wave instruction; no staging registers, no LDS stores): stage st + 2 is
+// requested while stage st is in the matrix pipe.  Per stage: wait for the wave's OWN loads of stage st (vmcnt(6): the six of stage st + 1 stay in
+// flight; vmcnt(0) on the last stage), one raw s_barrier (after it every wave's part of stage st is in LDS and every wave has finished reading
+// stage st - 1), request stage st + 2 into the slot of stage st - 1, then 2 x 9 operand reads and 2 x 18 (NW = 5: all nine digit products) or 2 x 16
+// (NW = 4: the product of the two lowest digits dropped) matrix instructions.  No __syncthreads() in the loop (it would drain the loads in flight),
+// no register-destination global load until the loop's last vmcnt(0), and all LDS in the caller's one dynamic array of GI_LDS_BYTES.
 // D[i][j] of acc[t][s]: j = lane & 31 (B operand), i = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (A operand).
 // Forced inline, and acc indexed with compile-time indices only: a call or a runtime index would put the accumulators in scratch.
 constexpr int GI_STAGE_BYTES = 2 * 3 * 4 * 4 * 512;  // side, digit, panel, row group
+constexpr int GI_SLOTS = 3;
+constexpr int GI_LDS_BYTES = GI_SLOTS * GI_STAGE_BYTES;  // dynamic LDS of every kernel that runs gi_tile_loop
+
+// piece q = r * 512 + tid of a stage in LDS order [side][digit][panel][row group][column]: r = 3 side + digit, tid = 128 panel + 32 row group + column
+__device__ __forceinline__ void gi_request_stage(const unsigned char* gA, int64_t strideA, const unsigned char* gB, int64_t strideB, unsigned char* wave_dst) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        const unsigned char* src = r < 3 ? gA + r * strideA : gB + (r - 3) * strideB;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)(wave_dst + r * 8192), 16, 0, 0);
+    }
+}
+
+// One stage out of the slot at `cur`; REQ: stage st + 2 is requested into `wave_fill` behind the first matrix instructions.  Order in the wave's
+// instruction stream, pinned with sched_group_barrier: the nine operand reads of the first half-stage, then its matrix instructions with the six
+// loads and the nine reads of the second half-stage one by one between them, then the rest.  What the compiler makes of it: lgkmcnt(0) after the
+// first nine reads, so the first matrix instruction of a stage still waits for that burst behind the barrier, and a second lgkmcnt(0) half-way,
+// by which the second half-stage's reads have long returned; only those are hidden.
+template <int NW, bool REQ>
+__device__ __forceinline__ void gi_stage(const unsigned char* cur, int lane, int wi, int wj, const unsigned char* gA, int64_t strideA, const unsigned char* gB,
+                                         int64_t strideB, unsigned char* wave_fill, i32x16 (&acc)[2][NW]) {
+    i32x4 fa[2][2][3], fb[2][3];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        if (ks == 1 && REQ) gi_request_stage(gA, strideA, gB, strideB, wave_fill);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) fa[ks][t][a] = *(const i32x4*)(cur + (((0 * 3 + a) * 4 + 2 * wi + t) * 4 + 2 * ks) * 512 + lane * 16);
+            fb[ks][a] = *(const i32x4*)(cur + (((1 * 3 + a) * 4 + wj) * 4 + 2 * ks) * 512 + lane * 16);
+        }
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+                    if (a + c < NW) acc[t][a + c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[ks][t][a], fb[ks][c], acc[t][a + c], 0, 0, 0);
+    constexpr int NM = NW >= 5 ? 18 : 16;  // matrix instructions per half-stage
+    __builtin_amdgcn_sched_group_barrier(0x100, 9, 0);  // DS read
+    if (REQ) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // VMEM
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM - 9 - (REQ ? 6 : 0), 0);
+}
+
 template <int NW>
 __device__ __forceinline__ void gi_tile_loop(const signed char* __restrict__ plA, int64_t strideA, int npA, const signed char* __restrict__ plB,
                                              int64_t strideB, int npB, int Ib, int Jb, int kgs, unsigned char* lds, i32x16 (&acc)[2][NW]) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wi = w >> 2, wj = w & 3;
-    // loader: piece q of a stage (16 bytes), q = round * 512 + tid, in LDS order [side][digit][panel][row group][column]
-    const unsigned char* gsrc[6];
-    bool gok[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const int q = r * 512 + tid;
-        const int side = q / 1536, qq = q % 1536;
-        const int a = (qq >> 7) >> 2, p4 = (qq >> 7) & 3, within = qq & 127;  // within: row group (2 bits) x column (5 bits)
-        const int P = 4 * (side ? Jb : Ib) + p4;
-        gok[r] = P < (side ? npB : npA);
-        gsrc[r] = (const unsigned char*)(side ? plB : plA) + (int64_t)a * (side ? strideB : strideA) + (int64_t)(gok[r] ? P : 0) * kgs * 512 + within * 16;
-    }
+    // loader: this thread's 16 bytes of panel tid >> 7 of either side, stage 0; a stage further on is 2048 bytes further on
+    const int p4 = tid >> 7, within = tid & 127;  // within: row group (2 bits) x column (5 bits)
+    const unsigned char* gA = (const unsigned char*)plA + (int64_t)min(4 * Ib + p4, npA - 1) * kgs * 512 + within * 16;
+    const unsigned char* gB = (const unsigned char*)plB + (int64_t)min(4 * Jb + p4, npB - 1) * kgs * 512 + within * 16;
+    unsigned char* const wdst = lds + w * 1024;  // wave-uniform destination; the lanes land at + 16 lane
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -104,41 +164,27 @@ __device__ __forceinline__ void gi_tile_loop(const signed char* __restrict__ plA
             for (int i = 0; i < 16; ++i) acc[t][s][i] = 0;
 
     const int nstage = kgs >> 2;
-    uint4 stg[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) stg[r] = gok[r] ? *(const uint4*)(gsrc[r]) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 6; ++r) *(uint4*)(lds + (r * 512 + tid) * 16) = stg[r];
-    __syncthreads();
-    for (int st = 0; st < nstage; ++st) {
-        const unsigned char* cur = lds + (st & 1) * GI_STAGE_BYTES;
-        if (st + 1 < nstage) {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) stg[r] = gok[r] ? *(const uint4*)(gsrc[r] + (int64_t)(st + 1) * 2048) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            i32x4 fa[2][3], fb[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-                    fa[t][a] = *(const i32x4*)(cur + (((0 * 3 + a) * 4 + 2 * wi + t) * 4 + 2 * ks) * 512 + lane * 16);
-                fb[a] = *(const i32x4*)(cur + (((1 * 3 + a) * 4 + wj) * 4 + 2 * ks) * 512 + lane * 16);
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        if (a + c < NW) acc[t][a + c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[t][a], fb[c], acc[t][a + c], 0, 0, 0);
-        }
-        if (st + 1 < nstage) {
-            unsigned char* nxt = lds + ((st + 1) & 1) * GI_STAGE_BYTES;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) *(uint4*)(nxt + (r * 512 + tid) * 16) = stg[r];
-        }
-        __syncthreads();
+    gi_request_stage(gA, strideA, gB, strideB, wdst);
+    if (nstage > 1) gi_request_stage(gA + 2048, strideA, gB + 2048, strideB, wdst + GI_STAGE_BYTES);
+    int cur_off = 0, fill_off = 2 * GI_STAGE_BYTES;  // slot of stage st; slot of stage st + 2 = that of stage st - 1
+    // lgkmcnt(0) with every wait: whatever the compiler moved, no operand read of the stage before is pending when this wave lets the others past
+    // the barrier to overwrite that stage's slot
+    for (int st = 0; st + 2 < nstage; ++st) {
+        gA += 2048;
+        gB += 2048;
+        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        gi_stage<NW, true>(lds + cur_off, lane, wi, wj, gA + 2048, strideA, gB + 2048, strideB, wdst + fill_off, acc);
+        cur_off = cur_off == 2 * GI_STAGE_BYTES ? 0 : cur_off + GI_STAGE_BYTES;
+        fill_off = fill_off == 2 * GI_STAGE_BYTES ? 0 : fill_off + GI_STAGE_BYTES;
     }
+    if (nstage > 1) {  // the last stage but one: nothing left to request, the last stage stays in flight
+        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        gi_stage<NW, false>(lds + cur_off, lane, wi, wj, gA, strideA, gB, strideB, wdst, acc);
+        cur_off = cur_off == 2 * GI_STAGE_BYTES ? 0 : cur_off + GI_STAGE_BYTES;
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    gi_stage<NW, false>(lds + cur_off, lane, wi, wj, gA, strideA, gB, strideB, wdst, acc);
 }

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(512) void nn_gemm_i8_kernel(TallBatch tb, const sig
                                                          const signed char* __restrict__ planesB, int64_t strideB, int jps, int cgs,
                                                          const int* __restrict__ aex, int rows_pad, const int* __restrict__ gex, int kp, int r0, int rows, int k,
                                                          int64_t ldo, int gx, int gy) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // 2 x GI_STAGE_BYTES
+    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // GI_LDS_BYTES
     const int z = blockIdx.y;
     float* __restrict__ out = tb.lng[z];
     if (!out) return;

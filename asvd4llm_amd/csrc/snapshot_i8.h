@@ -48,7 +48,7 @@ __global__ __launch_bounds__(512) void fullcheck_i8_kernel(const signed char* __
                                                            const int* __restrict__ ex, const float* __restrict__ dn, float tol, int kb,
                                                            unsigned char* __restrict__ pflag, unsigned* __restrict__ maxoff_bits,
                                                            const int* __restrict__ done, int nt) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // 2 x GI_STAGE_BYTES
+    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // GI_LDS_BYTES
     const int b = blockIdx.y;
     if (ld_flag(done + b)) return;
     int Ib, Jb;

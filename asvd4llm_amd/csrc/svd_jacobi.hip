@@ -264,6 +264,31 @@ __global__ void super_schedule_kernel(Sched sc, int ns, int nsteps, int npairs, 
     out[step * npairs + k] = (S < ns && T < ns) ? ((S << 16) | T) : -1;
 }
 
+// test hook asvd_test_i8_tile: gi_tile_loop alone (i8_digits.h), the raw accumulators of every 128 x 128 block of two plane sets, out[s][32 npA][32 npB] (int32).  grid (ceil(npB / 4), ceil(npA / 4)).
+template <int NW>
+__global__ __launch_bounds__(512) void i8_tile_test_kernel(const signed char* __restrict__ plA, int64_t strideA, int npA, const signed char* __restrict__ plB,
+                                                           int64_t strideB, int npB, int kgs, int* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gi_lds[];  // GI_LDS_BYTES
+    const int Ib = blockIdx.y, Jb = blockIdx.x;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wi = w >> 2, wj = w & 3;
+    i32x16 acc[2][NW];
+    gi_tile_loop<NW>(plA, strideA, npA, plB, strideB, npB, Ib, Jb, kgs, gi_lds, acc);
+    const int J = 4 * Jb + wj;
+    if (J >= npB) return;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int I = 4 * Ib + 2 * wi + t;
+        if (I >= npA) continue;
+#pragma unroll
+        for (int s = 0; s < NW; ++s)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int i = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                out[((int64_t)s * 32 * npA + I * 32 + i) * (32 * npB) + J * 32 + (lane & 31)] = acc[t][s][reg];
+            }
+    }
+}
+
 // what svd_tall and the split of a batch return when they do not apply: the caller then runs the plain call
 constexpr int NOT_APPLICABLE = -100;   // the reduction (Cholesky breakdown, workspace too small for it), or the split (workspace, sizes)
 constexpr int SPLIT_REFUSED = -101;    // the split: refused (another process on the device, a CU-masked caller stream, no CU-masked streams)
@@ -546,8 +571,8 @@ static int sparse_snapshot(const Direct& c, const std::vector<int>& host_done, S
             const int64_t plane_stride = (int64_t)p.nb * kgs * 512;
             split_i8_kernel<<<dim3(p.nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(c.X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, sex, 0,
                                                                                            kgs, spl, plane_stride, nullptr, c.done);
-            ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)fullcheck_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
-            fullcheck_i8_kernel<<<dim3(nt * (nt + 1) / 2, batch), 512, 2 * GI_STAGE_BYTES, st>>>(spl, plane_stride, p.nb, kgs, p.n_pad, sex, dnorm, c.tol, c.kb,
+            ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)fullcheck_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GI_LDS_BYTES));
+            fullcheck_i8_kernel<<<dim3(nt * (nt + 1) / 2, batch), 512, GI_LDS_BYTES, st>>>(spl, plane_stride, p.nb, kgs, p.n_pad, sex, dnorm, c.tol, c.kb,
                                                                                               c.pflag, c.maxoff, c.done, (int)nt);
         } else {
             fullcheck_kernel<<<dim3(nt, nt, batch), 256, 0, st>>>(c.sc, c.X, p.panel_stride, p.batch_stride, p.nb, p.m_pad, p.n_pad, dnorm, c.tol, c.kb, c.pflag,
@@ -870,7 +895,7 @@ static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_s
     const int64_t m64 = round_up64(m_pad, 64);
     const int nseg = (int)ceil_div64(m64, cap_rows);
     const int seg = (int)round_up64(ceil_div64(m64, nseg), 64);
-    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)gram_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
+    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)gram_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GI_LDS_BYTES));
     const int nt = (nb + 3) / 4, ntri = nt * (nt + 1) / 2;
     for (int s = 0; s < nseg; ++s) {
         const int r0 = s * seg;
@@ -880,7 +905,7 @@ static int launch_gram_i8(const float* Xp, int64_t panel_stride, int64_t batch_s
         const int64_t plane_stride = (int64_t)nb * kgs * 512;
         split_i8_kernel<<<dim3(nb, (unsigned)ceil_div64(kgs, 8), batch), 256, 0, st>>>(Xp, panel_stride, batch_stride, nb, m_pad, n_pad, ex, r0, kgs,
                                                                                        scratch, plane_stride, inv, nullptr);
-        gram_i8_kernel<<<dim3(ntri, batch), 512, 2 * GI_STAGE_BYTES, st>>>(scratch, plane_stride, nb, kgs, n_pad, inv ? exs : ex, G, ldg, gbs, s > 0 ? 1 : 0, nt,
+        gram_i8_kernel<<<dim3(ntri, batch), 512, GI_LDS_BYTES, st>>>(scratch, plane_stride, nb, kgs, n_pad, inv ? exs : ex, G, ldg, gbs, s > 0 ? 1 : 0, nt,
                                                                            dp);
     }
     ASVD_HIP_CHECK(hipGetLastError());
@@ -957,16 +982,19 @@ static int launch_nn_i8(const Plan& p, const TallLayout& t, char* wb, const Tall
     const int vrpc = (int)ceil_div64(p.cols, vchunks);
     vcolmax_kernel<<<dim3((unsigned)ceil_div64(k, 256), vchunks, zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vrpc, vmax, kp);
     split_v_i8_kernel<<<dim3(jps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(tb, p.cols, (int)k, k, bex, p.n_pad, vmax, kp, cgs, planesB, strideB, gex);
-    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)nn_gemm_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GI_STAGE_BYTES));
+    ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)nn_gemm_i8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GI_LDS_BYTES));
     int64_t seg = ((int64_t)8 * p.n_pad / 3) / 128 * 128;   // rows of X^T planes per problem that fit the Gs region
     if (seg > rows_pad) seg = rows_pad;
     for (int64_t r0 = 0; r0 < rows_pad; r0 += seg) {
         const int rps = (int)(std::min<int64_t>(seg, rows_pad - r0) / 32);
+        // seg and rows_pad are multiples of 128, so every block of the segment holds four real row panels: nn_gemm_i8_kernel tests rows only
+        // against p.rows, and a clamped A panel (gi_tile_loop) inside a segment would be stored
+        if (rps < 4 || (rps & 3)) return ASVD_E_BADARG;
         const int64_t strideA = (int64_t)rps * cgs * 512;
         split_xt_i8_kernel<<<dim3(rps, (unsigned)ceil_div64(cgs, 8), zb), 256, 0, st>>>(Xz, p.panel_stride, p.batch_stride, p.rows, rows_pad, bex, p.n_pad,
                                                                                       aex, (int)r0, cgs, planesA, strideA);
         const int gx = (int)ceil_div64(jps, 4), gy = (int)ceil_div64(rps, 4);
-        nn_gemm_i8_kernel<<<dim3(gx * gy, zb), 512, 2 * GI_STAGE_BYTES, st>>>(tb, planesA, strideA, rps, planesB, strideB, jps, cgs, aex, rows_pad, gex, kp,
+        nn_gemm_i8_kernel<<<dim3(gx * gy, zb), 512, GI_LDS_BYTES, st>>>(tb, planesA, strideA, rps, planesB, strideB, jps, cgs, aex, rows_pad, gex, kp,
                                                                              (int)r0, p.rows, (int)k, k, gx, gy);
     }
     return ASVD_OK;
@@ -1569,6 +1597,27 @@ int asvd_test_gram(const float* Xp, int64_t panel_stride, int64_t batch_stride, 
     colmaxexp_kernel<<<dim3(nb, batch), 256, 0, st>>>(Xp, panel_stride, batch_stride, m_pad, n_pad, ex, nullptr);
     return launch_gram_i8(Xp, panel_stride, batch_stride, nb, m_pad, n_pad, batch, G, n_pad, (int64_t)n_pad * n_pad, (signed char*)scratch, scratch_bytes, ex,
                           nullptr, nullptr, nullptr, seg_rows, st);
+}
+
+// Test hook: gi_tile_loop alone (i8_digits.h) over every 128 x 128 block of two caller-built plane sets; out: the raw accumulators
+// [nw][32 npA][32 npB] (int32).
+int asvd_test_i8_tile(const void* planesA, int64_t strideA, int npA, const void* planesB, int64_t strideB, int npB, int kgs, int nw, int* out,
+                      void* stream) {
+    if (!planesA || !planesB || !out || npA < 1 || npB < 1 || kgs < 4 || (kgs % 4) || kgs > 2048 || (nw != 4 && nw != 5)) return ASVD_E_BADARG;
+    if (strideA < (int64_t)npA * kgs * 512 || strideB < (int64_t)npB * kgs * 512) return ASVD_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)ceil_div64(npB, 4), (unsigned)ceil_div64(npA, 4));
+    const signed char* pa = (const signed char*)planesA;
+    const signed char* pb = (const signed char*)planesB;
+    if (nw == 5) {
+        ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)i8_tile_test_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, GI_LDS_BYTES));
+        i8_tile_test_kernel<5><<<grid, 512, GI_LDS_BYTES, st>>>(pa, strideA, npA, pb, strideB, npB, kgs, out);
+    } else {
+        ASVD_HIP_CHECK(hipFuncSetAttribute((const void*)i8_tile_test_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, GI_LDS_BYTES));
+        i8_tile_test_kernel<4><<<grid, 512, GI_LDS_BYTES, st>>>(pa, strideA, npA, pb, strideB, npB, kgs, out);
+    }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
 }
 
 // Test hook: the super-panel pair schedule itself.  out[step * npairs + k] = (S << 16) | T of slot k of super-step `step`, or -1 for an empty

@@ -435,6 +435,12 @@ int asvd_test_supgram(float* X, int64_t panel_stride, int64_t batch_stride, int 
  * tests/test_gpu_gram_i8.py only. */
 int asvd_test_gram(const float* Xp, int64_t panel_stride, int64_t batch_stride, int nb, int m_pad, int batch, int mode, int seg_rows, double* G,
                    void* scratch, size_t scratch_bytes, int* ex, void* stream);
+/* Test hook: the tile loop of the int8 digit-product kernels alone (csrc/i8_digits.h), with nw = 4 or 5 weights, over every 128 x 128 block of
+ * two plane sets in that file's layout ([digit][panel][16-index group][column][16 bytes], strideA / strideB bytes per digit, npA / npB panels,
+ * kgs 16-index groups: a multiple of 4, at most 2048).  out [nw][32 npA][32 npB] int32: out[s] = sum over a + c = s of (digit a of A)^T (digit c
+ * of B).  tests/test_gpu_i8_stage_ring.py only. */
+int asvd_test_i8_tile(const void* planesA, int64_t strideA, int npA, const void* planesB, int64_t strideB, int npB, int kgs, int nw, int* out,
+                      void* stream);
 /* Test hook: the super-panel pair schedule of the two-level sweeps for `ns` super-panels (grouped != 0: the grouped order where it applies,
  * else XOR).  out_dev: device int[out_capacity] >= nsteps * npairs; out[step * npairs + k] = (S << 16) | T or -1 (empty slot).
  * tests/test_gpu_twolevel.py only. */
