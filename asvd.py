@@ -27,6 +27,13 @@ def build_model(args):
     return model, tokenizer
 
 
+def check_weight_quant_args(args):
+    """flag combinations that are errors whatever the model; called before anything is loaded"""
+    if getattr(args, "weight_quant_mse", False) and not args.weight_quant.startswith("rtn_"):
+        raise ValueError(f"--weight_quant_mse is the clip search of the RTN quantizer: it needs --weight_quant rtn_int8, rtn_int6 or rtn_int4 "
+                         f"(got --weight_quant {args.weight_quant})")
+
+
 def run_weight_quant(model, args):
     """--weight_quant (asvd.py:49-58 of the reference), after the search and the factor gather.  Under --dist with --gather_factors rank0 only
     rank 0 holds the complete model; the other ranks stop before evaluation, so only rank 0 quantizes.  The result is per row (or per group of
@@ -40,6 +47,8 @@ def run_weight_quant(model, args):
     if group not in (0, 64, 128):
         raise ValueError(f"--weight_quant_group_size must be 0, 64 or 128 (got {group})")
     kw = {"group_size": group} if group else {}   # per row: exactly the calls made before the flag existed
+    if getattr(args, "weight_quant_mse", False):
+        kw["mse"] = True
     if storage == "bitpacked" and bits == 8:
         raise ValueError("--weight_quant_storage bitpacked with rtn_int8: 8-bit codes are already one per byte: use packed")
     if args.dist and args.gather_factors == "rank0" and int(os.environ.get("RANK", "0")) != 0:
@@ -60,6 +69,7 @@ def run_weight_quant(model, args):
 
 
 def main(args):
+    check_weight_quant_args(args)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
@@ -150,6 +160,10 @@ def build_parser():
                         help="rtn_*: 0 keeps one scale and zero per output row (the reference's RTN); 64 / 128 keep one pair per group of that many "
                              "input columns (8 bytes per group: 4.5 bits per weight for rtn_int4 with 128), which about halves the quantization "
                              "error of the ASVD factor pairs and is what makes rtn_int4 usable; valid with every storage")
+    parser.add_argument("--weight_quant_mse", action="store_true",
+                        help="rtn_*: take every scale and zero from the clip search of the reference's Quantizer (mse=True: 80 shrunk ranges per row "
+                             "or group, the smallest sum |q(x) - x|^2.4 wins) instead of the plain min / max; valid with every storage and group "
+                             "size, an error with awq_* or without --weight_quant")
     parser.add_argument("--eval_mmlu", action="store_true", help="evaluate mmlu")
     parser.add_argument("--eval_ppl", default="wikitext2,ptb", type=str)
     parser.add_argument("--eval_tasks", type=str, default="")

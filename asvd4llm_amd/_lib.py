@@ -58,6 +58,9 @@ SIGNATURES = {
     "asvd_rtn_quant_grouped": (_i, [_vp, _i, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
     "asvd_rtn_quant_grouped_batched": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64), _i,
                                             _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i64]),
+    "asvd_rtn_quant_mse_batched": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64), _i,
+                                        _c.POINTER(_vp), _c.POINTER(_i64), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i64,
+                                        _f, _i, _f]),
     "asvd_w8_linear_grouped_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "asvd_w8_dequant_grouped": (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i64, _vp]),
     "asvd_wb_dequant_grouped": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i64, _vp]),

@@ -16,7 +16,8 @@ A model whose weights were packed (`--weight_quant_storage packed`: W8Linear mod
 with `load_asvd_repo` only.  A model whose codes are stored at their own width (`--weight_quant_storage bitpacked`: WBLinear modules) is written
 the same way with `<layer>.qbits` (uint8 bitstream rows, modules/wb_linear.py) in place of `.qweight` and `"storage": "bitstream64"`.  One
 model holds one width and one storage form.  Group-wise scales (`--weight_quant_group_size G`) add `"group_size": G` to `weight_quant` and
-make `.scales` / `.zeros` [out, ceil(in / G)]; the key is absent for per-row scales, and one model holds one group size.
+make `.scales` / `.zeros` [out, ceil(in / G)]; the key is absent for per-row scales, and one model holds one group size.  The clip search (`--weight_quant_mse`) changes nothing on disk: it
+only gives `.scales` / `.zeros` other values, so the format has no key for it and a loaded model does not know whether its pairs were searched.
 """
 import json
 import os

@@ -416,16 +416,41 @@ def _check_params(what, scale, zero, rows, cols, group, dev):
         raise ValueError(f"{what} needs scale / zero [{rows}] fp32 contiguous on the device of the codes")
 
 
-def rtn_quant_batched(ws, bits, want_params=False, group_size=0):
+MSE_MAX_CANDIDATES = 256   # RTN_MAX_CAND of csrc/rtn_quant.hip
+
+
+def _mse_params(norm, grid, maxshrink):
+    """the clip search's parameters as asvd_rtn_quant_mse_batched accepts them: (norm, grid, maxshrink) as float, int, float"""
+    norm, maxshrink = float(norm), float(maxshrink)
+    if int(grid) != grid:
+        raise ValueError(f"mse_grid must be an integer (got {grid})")
+    grid = int(grid)
+    if not (0.0 < norm < float("inf")):
+        raise ValueError(f"mse_norm must be positive and finite (got {norm})")
+    if grid < 1:
+        raise ValueError(f"mse_grid must be at least 1 (got {grid})")
+    if not (0.0 < maxshrink <= 1.0):
+        raise ValueError(f"mse_maxshrink must be in (0, 1] (got {maxshrink})")
+    if not 1 <= int(maxshrink * grid) <= MSE_MAX_CANDIDATES:
+        raise ValueError(f"int(mse_maxshrink * mse_grid) must be in 1..{MSE_MAX_CANDIDATES} candidates (got {int(maxshrink * grid)})")
+    return norm, grid, maxshrink
+
+
+def rtn_quant_batched(ws, bits, want_params=False, group_size=0, mse=False, mse_norm=2.4, mse_grid=100, mse_maxshrink=0.8):
     """Round-to-nearest fake quantization (quantization.py:17-21,31-145 with perchannel=True, sym=False, mse=False) of a list of 2-D
     device tensors of any shapes, strides (unit column stride) and dtypes, ONE launch per 16 of them (asvd_rtn_quant_batched), then one
     host sync for the per-tensor flags.  Returns one entry per tensor: the quantized tensor (new, contiguous, same dtype) — or the input
     tensor itself when one of its rows has scale 0, which the reference leaves unchanged (Quantizer.ready()).  want_params: the entry is
     (out, q, scale, zero, flagged) with q the uint8 codes [rows, cols] (0 where q is NaN) and scale / zero fp32 [rows].
     group_size 64 / 128 (K14, asvd_rtn_quant_grouped_batched): every group of that many columns of a row is quantized as a row of its own;
-    scale / zero are [rows, ceil(cols / group_size)], and a tensor is flagged when one of its GROUPS has scale 0."""
+    scale / zero are [rows, ceil(cols / group_size)], and a tensor is flagged when one of its GROUPS has scale 0.
+    mse (K15, asvd_rtn_quant_mse_batched): the reference Quantizer's mse=True.  Every row (or group) tries int(mse_maxshrink * mse_grid) ranges
+    shrunk by p = 1 - i / mse_grid and keeps the scale / zero with the smallest sum |q(x) - x|^mse_norm (the lowest index among ties; a unit
+    with a NaN, an Inf or scale 0 keeps its min / max pair); everything else — shapes, flags, the arithmetic of out and q — is unchanged."""
     lib = L.load(True)
     group = _group(group_size)
+    if mse:
+        mse_args = _mse_params(mse_norm, mse_grid, mse_maxshrink)
     if not 1 <= int(bits) <= 8:
         raise ValueError(f"bits must be in 1..8 (got {bits})")
     ws = list(ws)
@@ -451,7 +476,9 @@ def rtn_quant_batched(ws, bits, want_params=False, group_size=0):
             i64(*[w.stride(0) for w in ws]), int(bits), ptrs(outs), i64(*[w.shape[1] for w in ws]), ptrs(scales) if want_params else None,
             ptrs(zeros) if want_params else None, ptrs(qs) if want_params else None, _ptr(flags), _stream(ws[0]))
     with _on(dev):
-        if group:
+        if mse:
+            L.check(lib.asvd_rtn_quant_mse_batched(*args, group, *mse_args), "asvd_rtn_quant_mse_batched")
+        elif group:
             L.check(lib.asvd_rtn_quant_grouped_batched(*args, group), "asvd_rtn_quant_grouped_batched")
         else:
             L.check(lib.asvd_rtn_quant_batched(*args), "asvd_rtn_quant_batched")
@@ -462,9 +489,9 @@ def rtn_quant_batched(ws, bits, want_params=False, group_size=0):
     return res
 
 
-def rtn_quant(w, bits, want_params=False, group_size=0):
+def rtn_quant(w, bits, want_params=False, group_size=0, mse=False, mse_norm=2.4, mse_grid=100, mse_maxshrink=0.8):
     """rtn_quant_batched for one tensor"""
-    return rtn_quant_batched([w], bits, want_params, group_size)[0]
+    return rtn_quant_batched([w], bits, want_params, group_size, mse, mse_norm, mse_grid, mse_maxshrink)[0]
 
 
 W8_MAX_TOKENS = 256  # ASVD_W8_MAX_TOKENS (asvd_w8_linear_max_tokens)

@@ -7,7 +7,9 @@ are left alone.  Here the weights of one block go through ONE batched launch (op
 reference's bit for bit.  `rtn_pack_sequential` is the same step with the weights kept as uint8 codes (modules/w8_linear.py) or, for 6 and 4 bits, as codes of their own
 width (modules/wb_linear.py).  `group_size` 64 / 128 gives both steps one scale and zero per group of that many input columns instead of per
 row (csrc K14): the reference has that only inside AutoAWQ (`q_group_size: 128`), and the factor pairs of ASVD, whose columns carry the
-falling sqrt(sigma), need it at 4 bits.  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
+falling sqrt(sigma), need it at 4 bits.  `mse=True` turns on the clip search of the reference's Quantizer (csrc K15; its defaults: norm 2.4,
+grid 100, maxshrink 0.8), which the reference's own RTN step leaves off: every row or group keeps the shrunk range with the smallest error instead
+of its min / max.  AWQ (`awq_quant_sequential`) needs the `awq` package and is not provided."""
 import torch
 import torch.nn as nn
 
@@ -41,13 +43,14 @@ def rtn_targets(model):
 
 
 @torch.no_grad()
-def rtn_quant_sequential(model, wbits, group_size=0):
+def rtn_quant_sequential(model, wbits, group_size=0, mse=False):
     """quantization.py:157-175: round-to-nearest `wbits`-bit fake quantization (per output row, asymmetric, no MSE search) of every
     nn.Linear weight in the decoder blocks, one batched launch per block.  A tensor with a row whose scale is 0 is left unchanged, as
     the reference's Quantizer.ready() check does.  The one-launch forward copies of every SVDLinear in a block are dropped
     (refresh_fused), so that they are rebuilt from the quantized factors.  Returns the number of weights replaced.
     group_size 64 / 128: every group of that many columns of a row is quantized as a row of its own (the Quantizer on the weight reshaped
-    to groups; the last group of a row is shorter when in_features is no multiple); a tensor with a group of scale 0 is left unchanged."""
+    to groups; the last group of a row is shorter when in_features is no multiple); a tensor with a group of scale 0 is left unchanged.
+    mse: the Quantizer's clip search (mse=True) per row or group, with the reference's defaults."""
     group_size = ops._group(group_size)
     blocks_name, blocks = find_decoder_blocks(model)
     if blocks is None:
@@ -60,7 +63,7 @@ def rtn_quant_sequential(model, wbits, group_size=0):
         subset = _find_linears(block)
         if not subset:
             continue
-        outs = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, group_size=group_size)
+        outs = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, group_size=group_size, mse=bool(mse))
         for (_, lin), out in zip(subset, outs):
             if out is not lin.weight.data:
                 n_done += 1
@@ -68,12 +71,16 @@ def rtn_quant_sequential(model, wbits, group_size=0):
         for m in block.modules():
             if isinstance(m, SVDLinear):
                 m.refresh_fused()
-    print(f"rtn int{wbits}{_group_tag(group_size)}: {n_done} weights quantized in {len(blocks)} blocks of {blocks_name}")
+    print(f"rtn int{wbits}{_group_tag(group_size)}{_mse_tag(mse)}: {n_done} weights quantized in {len(blocks)} blocks of {blocks_name}")
     return n_done
 
 
 def _group_tag(group_size):
     return f" g{group_size}" if group_size else ""
+
+
+def _mse_tag(mse):
+    return " mse" if mse else ""
 
 
 def _set_submodule(root, name, new):
@@ -82,7 +89,7 @@ def _set_submodule(root, name, new):
 
 
 @torch.no_grad()
-def rtn_pack_sequential(model, wbits, storage="bytes", group_size=0):
+def rtn_pack_sequential(model, wbits, storage="bytes", group_size=0, mse=False):
     """rtn_quant_sequential with the result kept PACKED: per decoder block one batched launch that also emits the uint8 codes and the per-row
     fp32 scale / zero, and every target nn.Linear replaced by a W8Linear holding them (one byte per weight for any wbits <= 8; the bias is
     kept as it is).  The packed layer stands for exactly the fake-quantized weight: W8Linear.dequantize() is the `out` of the launch, bit
@@ -92,7 +99,9 @@ def rtn_pack_sequential(model, wbits, storage="bytes", group_size=0):
     storage="bits" (wbits 6 or 4 only): the codes of the launch are packed to their own width (ops.wb_pack), the byte codes released and the
     layer becomes a WBLinear; the check is the same, on what ops.wb_dequant reads back from the bit-packed rows.
     group_size 64 / 128: scale / zero per group of that many columns ([out, ceil(in / group_size)] each, 8 bytes per group in the byte count);
-    the modules carry the group size and the check is the same."""
+    the modules carry the group size and the check is the same.
+    mse: the scale / zero of every row or group come from the Quantizer's clip search; the modules, the check and the byte count see only other
+    values."""
     if storage not in ("bytes", "bits"):
         raise ValueError(f"storage must be 'bytes' or 'bits' (got {storage!r})")
     if storage == "bits" and int(wbits) not in WB_BITS:
@@ -109,7 +118,7 @@ def rtn_pack_sequential(model, wbits, storage="bytes", group_size=0):
         subset = _find_linears(block)
         if not subset:
             continue
-        res = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, want_params=True, group_size=group_size)
+        res = ops.rtn_quant_batched([lin.weight.data for _, lin in subset], wbits, want_params=True, group_size=group_size, mse=bool(mse))
         bad, packed = [], []
         for (_, lin), (out, q, scale, zero, flagged) in zip(subset, res):
             packed.append(ops.wb_pack(q, wbits) if storage == "bits" and not flagged else None)
@@ -139,5 +148,5 @@ def rtn_pack_sequential(model, wbits, storage="bytes", group_size=0):
         for m in block.modules():
             if isinstance(m, SVDLinear):
                 m.refresh_fused()
-    print(f"rtn int{wbits}{_group_tag(group_size)} {'bit-packed' if storage == 'bits' else 'packed'}: {n_packed} weights in {len(blocks)} blocks, {bytes_before} -> {bytes_after} bytes")
+    print(f"rtn int{wbits}{_group_tag(group_size)}{_mse_tag(mse)} {'bit-packed' if storage == 'bits' else 'packed'}: {n_packed} weights in {len(blocks)} blocks, {bytes_before} -> {bytes_after} bytes")
     return n_packed

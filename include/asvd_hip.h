@@ -364,6 +364,24 @@ int asvd_wb_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t 
                                int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K15  RTN with the clip search of the reference's Quantizer (quantization.py:94-111, mse=True).  A unit is a row (group 0) or a group of 64 / 128
+ *   columns.  Its base pair (scale, zero) is that of K11 / K14.  Candidate i = 0 .. n - 1, n = int(maxshrink * grid) as Python computes it in
+ *   double, shrinks the range: p = float(1 - i / grid) (double arithmetic, one cast), xmin1 = p xmin, xmax1 = p xmax,
+ *   scale1 = (xmax1 - xmin1) / maxq, zero1 = rint(-xmin1 / scale1), each operation rounded to fp32 on its own.  The pair kept is the one with
+ *   the smallest sum over the unit of |scale1 (clamp(rint(x / scale1) + zero1, 0, maxq) - zero1) - x|^norm; a candidate replaces the best so far
+ *   only when its sum is strictly smaller, so the lowest index wins ties and a NaN or infinite sum never wins.  A unit whose base scale is 0,
+ *   infinite or NaN keeps its base pair and is flagged or poisoned as without the search.  The sums are evaluated with a hardware reciprocal,
+ *   exp2(norm log2|d|) and a fixed order of additions: the choice among near-tied candidates may differ from an fp64 evaluation by that much,
+ *   and two calls give the same bits.  out, codes, scale and zero are then written as by K11 / K14 with the chosen pair, in the same arithmetic.
+ * asvd_rtn_quant_mse_batched:  the arguments of asvd_rtn_quant_grouped_batched (group 0, 64 or 128), then the search's norm (2.4 in the
+ *   reference), grid (100) and maxshrink (0.8).  ASVD_E_BADARG before any device call for norm <= 0 or not finite, grid < 1, maxshrink outside
+ *   (0, 1], or a candidate count outside 1 .. 256.  maxshrink is read as the shortest decimal that gives that float (0.7f counts as 0.7). */
+int asvd_rtn_quant_mse_batched(int batch, const void* const* w_host, const int* dtype_host, const int64_t* rows_host, const int64_t* cols_host,
+                               const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
+                               float* const* zero_host, void* const* codes_host, int* flags, void* stream, int64_t group, float norm, int grid,
+                               float maxshrink);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's
