@@ -32,6 +32,7 @@
 // Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
 // with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
 #include "common.h"
+#include "grid_sync.h"
 #include <atomic>
 
 // every operation rounds on its own (the fake quantizer's `scale * (q - zero)` is a subtraction, then a product)
@@ -123,7 +124,7 @@ __device__ __forceinline__ f32x16 w8_mfma(const uint4& a, const uint4& b, f32x16
 }
 
 // one iteration of a lane: its 64 codes (8 BITS bytes) and 64 x values (16-byte loads), and the 8 MFMAs that consume them
-template <int BITS>
+template <int BITS, bool XCOH>
 __device__ __forceinline__ void w8_iter_load(uint4 (&cv)[W8_CW<BITS>], uint4 (&xv)[8], const uint8_t* __restrict__ qrow, const uint16_t* __restrict__ xr,
                                              int it) {
     const uint4* cp = (const uint4*)(qrow + (int64_t)it * (W8_KIT * BITS / 8));
@@ -131,7 +132,10 @@ __device__ __forceinline__ void w8_iter_load(uint4 (&cv)[W8_CW<BITS>], uint4 (&x
 #pragma unroll
     for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cp[m];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) xv[m] = xp[m];
+    for (int m = 0; m < 8; ++m) {
+        if constexpr (XCOH) xv[m] = z_load16(xp + m);   // the intermediate of the packed pair (K16), written in this launch: agent-scope loads
+        else xv[m] = xp[m];
+    }
 }
 
 template <int BITS>
@@ -148,18 +152,20 @@ __device__ __forceinline__ f32x16 w8_iter_mfma(const uint4 (&cv)[W8_CW<BITS>], c
     return acc;
 }
 
+// One (32-token, ft-feature) tile of y = fp16(x w^T + bias), tokens t0.., features n0.., by the whole workgroup: the tile loop, the LDS
+// reduction in its fixed order, bias and store.  w8_linear_kernel is one call of it; the packed pair calls it once per unit of a phase (the
+// caller separates two calls by a __syncthreads(): red is reused).
 // BITS = 8: q holds one code per byte, ldq >= K.  BITS = 6, 4: q holds the bitstream rows (ldq bytes apart), K % 16 == 0 and everything is
-// 16-byte aligned (vec is 1).  GROUPED: scale / zero are [N, ng], a group is 1 << gshift codes; K % 16 == 0 and vec is 1 at every width
-template <int BITS, bool GROUPED>
-__global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
-                                                              const float* __restrict__ scale, const float* __restrict__ zero,
-                                                              const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ft,
-                                                              int nkfull /* whole iterations that take 16-byte loads */, int vec /* rows are 16-byte aligned */,
-                                                              int ng, int gshift) {
-    __shared__ float red[W8_WAVES][16 * 64];
+// 16-byte aligned (vec is 1).  GROUPED: scale / zero are [N, ng], a group is 1 << gshift codes; K % 16 == 0 and vec is 1 at every width.
+// XCOH: x is the pair's intermediate (z_load16; vec is 1 and K % 16 == 0, no element loads of x).  ZOUT: y is that intermediate (z_store).
+template <int BITS, bool GROUPED, bool XCOH, bool ZOUT>
+__device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
+                                        const float* __restrict__ scale, const float* __restrict__ zero, const uint16_t* __restrict__ bias, int N,
+                                        int K, uint16_t* __restrict__ y, int t0, int n0, int ft,
+                                        int nkfull /* whole iterations that take 16-byte loads */, int vec /* rows are 16-byte aligned */, int ng,
+                                        int gshift) {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int i = lane & 31, g = lane >> 5;
-    const int n0 = blockIdx.x * ft, t0 = blockIdx.y * 32;
     const int nvalid = min(ft, N - n0), tvalid = min(32, T - t0);
     const int wrow = n0 + min(i, nvalid - 1), xrow = t0 + min(i, tvalid - 1);
     float sc = 0.f, zr = 0.f;
@@ -181,7 +187,7 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
         float gs[W8_U], gz[W8_U];   // GROUPED: in flight with the code loads of the group (a whole iteration lies within K: the index is < ng)
 #pragma unroll
         for (int u = 0; u < W8_U; ++u) {
-            w8_iter_load<BITS>(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
+            w8_iter_load<BITS, XCOH>(cv[u], xv[u], qrow, xr, base + W8_WAVES * u);
             if constexpr (GROUPED) {
                 const int gi = ((base + W8_WAVES * u) * W8_KIT + 64 * g) >> gshift;
                 gs[u] = srow[gi], gz[u] = zrow[gi];
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
     }
     for (; base < nkfull; base += W8_WAVES) {
         uint4 cv[W8_CW<BITS>], xv[8];
-        w8_iter_load<BITS>(cv, xv, qrow, xr, base);
+        w8_iter_load<BITS, XCOH>(cv, xv, qrow, xr, base);
         if constexpr (GROUPED) {
             const int gi = (base * W8_KIT + 64 * g) >> gshift;
             sc = srow[gi], zr = zrow[gi];
@@ -225,12 +231,21 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
             uint4 x0, x1;
             if (BITS != 8) {   // K % 16 == 0: a chunk is whole or absent; the padding codes of an absent one are masked below, x is zero
                 w8_chunk_words<BITS>(cv, m, w);
-                x0 = valid == 16 ? ((const uint4*)xp)[0] : make_uint4(0, 0, 0, 0);
-                x1 = valid == 16 ? ((const uint4*)xp)[1] : make_uint4(0, 0, 0, 0);
+                if constexpr (XCOH) {
+                    x0 = valid == 16 ? z_load16((const uint4*)xp) : make_uint4(0, 0, 0, 0);
+                    x1 = valid == 16 ? z_load16((const uint4*)xp + 1) : make_uint4(0, 0, 0, 0);
+                } else {
+                    x0 = valid == 16 ? ((const uint4*)xp)[0] : make_uint4(0, 0, 0, 0);
+                    x1 = valid == 16 ? ((const uint4*)xp)[1] : make_uint4(0, 0, 0, 0);
+                }
             } else {
                 const uint8_t* cp = qrow + (int64_t)it * W8_KIT + 16 * m;
                 uint4 c;
-                if (vec && valid == 16) {   // a whole chunk of aligned rows (K % 128 >= 16): 16-byte loads here too
+                if constexpr (XCOH) {   // aligned rows and K % 16 == 0: a chunk is whole or absent
+                    c = valid == 16 ? *(const uint4*)cp : make_uint4(0, 0, 0, 0);
+                    x0 = valid == 16 ? z_load16((const uint4*)xp) : make_uint4(0, 0, 0, 0);
+                    x1 = valid == 16 ? z_load16((const uint4*)xp + 1) : make_uint4(0, 0, 0, 0);
+                } else if (vec && valid == 16) {   // a whole chunk of aligned rows (K % 128 >= 16): 16-byte loads here too
                     c = *(const uint4*)cp;
                     x0 = ((const uint4*)xp)[0];
                     x1 = ((const uint4*)xp)[1];
@@ -260,9 +275,63 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
         if (col < nvalid && row < tvalid) {
             float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
             if (bias) v += f16_bits_to_f32(bias[n0 + col]);
-            y[(int64_t)(t0 + row) * N + n0 + col] = f32_to_f16_bits(v);
+            if constexpr (ZOUT) z_store(y + (int64_t)(t0 + row) * N + n0 + col, f32_to_f16_bits(v));
+            else y[(int64_t)(t0 + row) * N + n0 + col] = f32_to_f16_bits(v);
         }
     }
+}
+
+template <int BITS, bool GROUPED>
+__global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
+                                                              const float* __restrict__ scale, const float* __restrict__ zero,
+                                                              const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ft,
+                                                              int nkfull, int vec, int ng, int gshift) {
+    __shared__ float red[W8_WAVES][16 * 64];
+    w8_tile<BITS, GROUPED, false, false>(red, x, T, q, ldq, scale, zero, bias, N, K, y, blockIdx.y * 32, blockIdx.x * ft, ft, nkfull, vec, ng, gshift);
+}
+
+// ---- K16: a packed SVDLinear factor pair in one launch --------------------------------------------------------------------------------
+//   z[T, r] = fp16( x[T, K] . wB^T )            phase 1, a unit = (token tile, ft1 rows of B)
+//   grid barrier (grid <= #CUs: co-resident; bounded spin, give-up word, NaN poison: grid_sync.h)
+//   y[T, N] = fp16( z . wA^T + bias )           phase 2, a unit = (token tile, ft2 rows of A)
+// Both phases are w8_tile, so every element of z and of y sees the operations of w8_linear_kernel on the same operands (iteration `it` belongs
+// to wave it % 4, chunk m to MFMA m, and the order of the LDS reduction does not depend on the workgroup or on ft): the launch returns the
+// bits of the two launches it replaces.  z ([round_up(T, 32), r] fp16 behind the 256-byte barrier block of the workspace) is stored and loaded
+// at agent scope; rows at or beyond T and nothing else of it stay unwritten and are never read (token rows are clamped as in the tile loop).
+// A workgroup takes units blockIdx.x, + gridDim.x, ...; one without a unit in a phase still arrives at the barrier.
+template <int BITS, bool GROUPED>
+__global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ qB,
+                                                                      int64_t ldB, const float* __restrict__ scaleB, const float* __restrict__ zeroB,
+                                                                      const uint8_t* __restrict__ qA, int64_t ldA, const float* __restrict__ scaleA,
+                                                                      const float* __restrict__ zeroA, const uint16_t* __restrict__ bias, int N, int K,
+                                                                      int r, uint16_t* __restrict__ y, uint16_t* z, unsigned* bar, int ft1, int ft2,
+                                                                      int gshift) {
+    __shared__ float red[W8_WAVES][16 * 64];
+    const int nT = (T + 31) / 32, G = gridDim.x;
+    const int ns1 = (r + ft1 - 1) / ft1, ns2 = (N + ft2 - 1) / ft2;
+    const int ngB = GROUPED ? (K + (1 << gshift) - 1) >> gshift : 1, ngA = GROUPED ? (r + (1 << gshift) - 1) >> gshift : 1;
+
+    for (int u = blockIdx.x; u < nT * ns1; u += G) {
+        w8_tile<BITS, GROUPED, false, true>(red, x, T, qB, ldB, scaleB, zeroB, nullptr, r, K, z, (u / ns1) * 32, (u % ns1) * ft1, ft1, K / W8_KIT, 1,
+                                            ngB, gshift);
+        __syncthreads();
+    }
+
+    grid_barrier(bar, (unsigned)G);
+
+    for (int u = blockIdx.x; u < nT * ns2; u += G) {
+        w8_tile<BITS, GROUPED, true, false>(red, z, T, qA, ldA, scaleA, zeroA, bias, N, r, y, (u / ns2) * 32, (u % ns2) * ft2, ft2, r / W8_KIT, 1,
+                                            ngA, gshift);
+        __syncthreads();
+    }
+    if (gave_up(bar))   // poison this workgroup's own tiles
+        for (int u = blockIdx.x; u < nT * ns2; u += G) {
+            const int t0 = (u / ns2) * 32, n0 = (u % ns2) * ft2, nvalid = min(ft2, N - n0);
+            for (int e = threadIdx.x; e < 1024; e += W8_THREADS) {
+                const int row = e >> 5, col = e & 31;
+                if (col < nvalid && t0 + row < T) y[(int64_t)(t0 + row) * N + n0 + col] = 0x7e00;  // fp16 NaN
+            }
+        }
 }
 
 // ---- dequantization to a dense weight ---------------------------------------------------------------------------------------------
@@ -510,9 +579,57 @@ int wb_linear_launch(const void* x, int64_t T, const void* q, int64_t ld_bytes, 
     return ASVD_OK;
 }
 
+template <int BITS, bool GROUPED>
+void lowrank_packed_go(int grid, hipStream_t stream, const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB,
+                       const void* qA, int64_t ldA, const float* scaleA, const float* zeroA, const void* bias, int64_t N, int64_t K, int64_t r, void* y,
+                       void* work, int ft1, int ft2, int gshift) {
+    hipLaunchKernelGGL((lowrank_packed_kernel<BITS, GROUPED>), dim3((unsigned)grid), dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T,
+                       (const uint8_t*)qB, ldB, scaleB, zeroB, (const uint8_t*)qA, ldA, scaleA, zeroA, (const uint16_t*)bias, (int)N, (int)K, (int)r,
+                       (uint16_t*)y, (uint16_t*)((char*)work + 256), (unsigned*)work, ft1, ft2, gshift);
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t asvd_lowrank_packed_work_bytes(int64_t T, int64_t r) {
+    // [barrier: 256 bytes][z: 32 * ceil(T / 32) x r fp16]
+    return 256 + (size_t)(round_up64(T, 32) * r) * sizeof(uint16_t);
+}
+
+int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB, const void* qA,
+                            int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias, int64_t N, int64_t K,
+                            int64_t r, void* y, void* work, size_t work_bytes, void* stream) {
+    if (!x || !qB || !scaleB || !zeroB || !qA || !scaleA || !zeroA || !y || !work) return ASVD_E_BADARG;
+    if (T < 1 || T > ASVD_W8_MAX_TOKENS || (bits != 8 && bits != 6 && bits != 4) || (group != 0 && group != 64 && group != 128)) return ASVD_E_BADARG;
+    if (N < 1 || K < 1 || r < 1 || K % 16 || r % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256 || r > 0x7fffffff - 256) return ASVD_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)qB | (uintptr_t)qA | (uintptr_t)work) % 16 || ldB % 16 || ldA % 16) return ASVD_E_BADARG;   // 16-byte loads only
+    if (ldB < (bits == 8 ? K : wb_row_bytes(K, bits)) || ldA < (bits == 8 ? r : wb_row_bytes(r, bits))) return ASVD_E_BADARG;
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (work_bytes < asvd_lowrank_packed_work_bytes(T, r)) return ASVD_E_WORKSPACE;
+    int cus = 0;
+    const int st = w8_cu_count(&cus);
+    if (st != ASVD_OK) return st;
+    const int nT = (int)((T + 31) / 32);
+    const int ft1 = w8_feature_tile(nT, r, cus), ft2 = w8_feature_tile(nT, N, cus);
+    const int64_t units1 = nT * ceil_div64(r, ft1), units2 = nT * ceil_div64(N, ft2), units = units1 > units2 ? units1 : units2;
+    const int grid = (int)(units < cus ? units : cus);   // <= one workgroup per CU: co-resident, the in-kernel barrier cannot deadlock
+    const int gshift = group == 64 ? 6 : 7;
+#define ASVD_LRP_GO(B, GR) lowrank_packed_go<B, GR>(grid, (hipStream_t)stream, x, T, qB, ldB, scaleB, zeroB, qA, ldA, scaleA, zeroA, bias, N, K, r, y, \
+                                                   work, ft1, ft2, gshift)
+    if (group) {
+        if (bits == 8) ASVD_LRP_GO(8, true);
+        else if (bits == 6) ASVD_LRP_GO(6, true);
+        else ASVD_LRP_GO(4, true);
+    } else {
+        if (bits == 8) ASVD_LRP_GO(8, false);
+        else if (bits == 6) ASVD_LRP_GO(6, false);
+        else ASVD_LRP_GO(4, false);
+    }
+#undef ASVD_LRP_GO
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
 
 int64_t asvd_w8_linear_max_tokens(void) { return ASVD_W8_MAX_TOKENS; }
 

@@ -16,6 +16,8 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import AsvdHipError
+from .w8_linear import W8Linear
+from .wb_linear import WBLinear
 
 # set ASVD_STRICT=1 (benchmarks / tests do) to raise instead of silently substituting a random Linear
 def _strict():
@@ -30,6 +32,32 @@ def _fused_forward_enabled():
     COPIES of the two factors, so it must only be used on weights that are no longer edited through `.data` (such edits do not bump
     Parameter._version and cannot be seen without reading the weights; call `refresh_fused()` after one)."""
     return os.environ.get("ASVD_FUSED_FORWARD", "0") == "1"
+
+
+# Token count up to which a pair of packed factors takes the one-launch forward (K16, ops.lowrank_packed_forward) when it is switched on.
+# The value is the packed kernels' own dispatch limit (W8_FORWARD_MAX_TOKENS / WB_FORWARD_MAX_TOKENS), not a crossover: MEASURED SLOWER than the two
+# launches at every token count (tools/bench_w8_forward.py --fused_pair --tokens 1,4,16 on MI355X, profiles/w8_fused_pair.json, DESIGN.md section 4,
+# K16: 1.51 / 1.70 / 1.92 of the two-launch time at 1 / 4 / 16 tokens in graph time at 8 bits per row, 1.39 / 1.55 / 1.76 at 4 bits with G = 128).  The
+# path claims no speed and stays opt-in; it gives the two-launch bits in one launch.
+FUSED_PACKED_MAX_TOKENS = 16
+
+
+def _fused_packed_enabled():
+    """The one-launch forward of a PACKED factor pair is opt-in too (ASVD_FUSED_PACKED=1, or `module.fused_packed = True` on one SVDLinear),
+    separately from ASVD_FUSED_FORWARD: it reads the modules' own buffers (nothing can go stale), but like K10 it is a persistent launch whose
+    workgroups must be co-resident, which is the caller's to know."""
+    return os.environ.get("ASVD_FUSED_PACKED", "0") == "1"
+
+
+def _without_hooks(mod):
+    import torch.nn.modules.module as _m
+    return not (mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks or _m._global_forward_hooks
+                or _m._global_forward_pre_hooks or _m._global_backward_hooks or _m._global_backward_pre_hooks)
+
+
+def _storage_bits(mod):
+    """bits a code occupies in the module's buffer: 8 in a W8Linear whatever the quantizer's width, the code width in a WBLinear"""
+    return 8 if type(mod) is W8Linear else mod.bits
 
 
 def _plain_linear_without_hooks(mod):
@@ -320,8 +348,9 @@ class SVDLinear(nn.Module):
         return new_linear
 
     def refresh_fused(self):
-        """drop the padded factor copies of the one-launch forward (rebuilt on the next decode-sized call)"""
+        """drop the padded factor copies of the one-launch forward (rebuilt on the next decode-sized call) and the workspaces of the packed pair"""
         self._fused = None
+        self._fused_packed = {}
 
     def check_fused_forward(self):
         """Read (one host sync per workspace) and clear the give-up flag of every one-launch-forward workspace of this module; raises AsvdHipError when
@@ -331,6 +360,54 @@ class SVDLinear(nn.Module):
         if st is not None:
             for work in st[3].values():
                 ops.lowrank_check(work)
+        for work in (getattr(self, "_fused_packed", None) or {}).values():
+            ops.lowrank_check(work)
+
+    def fused_packed_refusal(self, inp):
+        """Why `inp` takes the two calls BLinear, ALinear: a short reason, or None when it takes the one-launch packed pair (K16).  The fused call
+        replaces both factors' forward(), so it is taken only when that is all that would run and both would take their kernel: the switch is on,
+        the factors are exactly two W8Linear or two WBLinear of one storage width and one group size, BLinear has no bias, nothing is hooked on
+        (the factors or the module registry: calibration hooks of a compressed model keep running), and the conditions of both factors'
+        _kernel_input hold up to FUSED_PACKED_MAX_TOKENS tokens."""
+        A, B = self.ALinear, self.BLinear
+        if not (getattr(self, "fused_packed", False) or _fused_packed_enabled()):
+            return "switched off"
+        if not ((type(A) is W8Linear and type(B) is W8Linear) or (type(A) is WBLinear and type(B) is WBLinear)):
+            return "not a pair of W8Linear or a pair of WBLinear"
+        if _storage_bits(A) != _storage_bits(B):
+            return "different storage widths"
+        if A.group_size != B.group_size:
+            return "different group sizes"
+        if B.bias is not None:
+            return "BLinear has a bias"
+        if not (_without_hooks(A) and _without_hooks(B)):
+            return "hooks"
+        tokens = inp.numel() // inp.shape[-1] if inp.shape[-1] else 0
+        if not 0 < tokens <= FUSED_PACKED_MAX_TOKENS:
+            return "token count"
+        if not (inp.dtype == torch.float16 and A.weight_dtype == torch.float16 and B.weight_dtype == torch.float16
+                and (A.bias is None or A.bias.dtype == torch.float16)):
+            return "not fp16"
+        if inp.shape[-1] != B.in_features or A.in_features != B.out_features:
+            return "shapes"
+        if not (A.kernel_rows_ok() and B.kernel_rows_ok()):
+            return "code rows without 16-byte loads"
+        if torch.is_grad_enabled() and inp.requires_grad:
+            return "autograd"
+        if not (inp.is_cuda and A.scales.device == inp.device and B.scales.device == inp.device):
+            return "not on the device"
+        return None
+
+    def _fused_packed_work(self, x2d):
+        """ONE barrier / intermediate workspace per stream (two launches in flight must not share barrier words), created on first use"""
+        works = getattr(self, "_fused_packed", None)
+        if works is None:
+            works = self._fused_packed = {}
+        sid = torch.cuda.current_stream(x2d.device).cuda_stream
+        work = works.get(sid)
+        if work is None or work.device != x2d.device:
+            work = works[sid] = ops.lowrank_packed_work(FUSED_PACKED_MAX_TOKENS, self.BLinear.out_features, x2d.device)
+        return work
 
     def _fused_state(self, stream_id):
         """Padded copies of the two factors for the one-launch forward (ops.lowrank_pack), rebuilt when either Parameter is replaced or
@@ -354,7 +431,8 @@ class SVDLinear(nn.Module):
         # profiles/r5_k10_nostrict.jsonl; under ASVD_STRICT the wrapper used to read the give-up flag after every launch: +18 us, now every 64th).  Everywhere
         # else the reference's two GEMMs through nn.Linear: at par from 64 tokens on and on the 11008-wide MLP projections (DESIGN.md
         # section 4 has the table).  Opt-in (ASVD_FUSED_FORWARD=1 / self.fused_forward): see _fused_forward_enabled.
-        # (the plain-nn.Linear test comes before anything reads `.weight`: packed factors, modules/w8_linear.py, have none and fall through)
+        # (the plain-nn.Linear test comes before anything reads `.weight`: packed factors, modules/w8_linear.py, have none and fall through to the
+        # packed pair below, which has a switch of its own)
         if ((getattr(self, "fused_forward", False) or _fused_forward_enabled()) and inp.is_cuda and inp.dtype == torch.float16
                 and _plain_linear_without_hooks(self.ALinear) and _plain_linear_without_hooks(self.BLinear) and self.BLinear.bias is None
                 and self.BLinear.weight.dtype == torch.float16 and inp.shape[-1] % 64 == 0
@@ -364,6 +442,16 @@ class SVDLinear(nn.Module):
             x2d = inp.reshape(-1, inp.shape[-1])
             y = ops.lowrank_forward(x2d if x2d.is_contiguous() else x2d.contiguous(), Ap, Bp, self.ALinear.bias, work)
             return y.view(*inp.shape[:-1], y.shape[-1])
+        # a pair of packed factors (modules/w8_linear.py, modules/wb_linear.py), opt-in (ASVD_FUSED_PACKED=1 / self.fused_packed): ONE launch that
+        # returns the bits of the two calls below (K16, csrc/w8_linear.hip); fused_packed_refusal has the conditions
+        if self.fused_packed_refusal(inp) is None:
+            A, B = self.ALinear, self.BLinear
+            x2d = B._kernel_input(inp, FUSED_PACKED_MAX_TOKENS)   # None: a misaligned view
+            if x2d is not None:
+                wb = type(B) is WBLinear
+                y = ops.lowrank_packed_forward(x2d, B.qbits if wb else B.qweight, B.scales, B.zeros, A.qbits if wb else A.qweight, A.scales, A.zeros,
+                                               _storage_bits(B), A.bias, self._fused_packed_work(x2d), group_size=B.group_size)
+                return y.view(*inp.shape[:-1], A.out_features)
         y = self.BLinear(inp)
         y = self.ALinear(y)
         return y

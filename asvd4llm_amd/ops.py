@@ -327,8 +327,9 @@ def lowrank_check(work):
     flags = work[:16].view(torch.int32)
     if int(flags[2].item()) != 0:
         flags[2] = 0
-        raise L.AsvdHipError("asvd_lowrank_forward_f16: a workgroup gave up at the in-kernel grid barrier (the launch was not fully resident); "
-                             "its output was poisoned with NaN.  Use the two nn.Linear GEMMs (fused_forward = False) next to persistent kernels of other streams.")
+        raise L.AsvdHipError("asvd_lowrank_forward_f16 / asvd_lowrank_packed_f16: a workgroup gave up at the in-kernel grid barrier (the launch was not "
+                             "fully resident); its output was poisoned with NaN.  Use the two launches (fused_forward / fused_packed = False) next to "
+                             "persistent kernels of other streams.")
 
 
 def lowrank_forward(x2d, Ap, Bp, bias, work):
@@ -348,12 +349,17 @@ def lowrank_forward(x2d, Ap, Bp, bias, work):
     # two GEMMs" under ASVD_STRICT for exactly that reason).  ASVD_STRICT checks every 64th launch OF EACH WORKSPACE (the counter is keyed by
     # the workspace: with one global counter only the modules that happened to make a 64th call were ever checked — ADVICE r5), ASVD_DEBUG
     # every launch; lowrank_check(work) reads it on demand (SVDLinear.check_fused_forward: call it at the end of a generate / eval loop).
+    _lowrank_count(work)
+    return y
+
+
+def _lowrank_count(work):
+    """one more launch on `work`; reads its give-up word under ASVD_DEBUG (every launch) and ASVD_STRICT (every 64th launch of the workspace)"""
     key = work.data_ptr()
     n = _LOWRANK_CALLS.get(key, 0) + 1
     _LOWRANK_CALLS[key] = n
     if os.environ.get("ASVD_DEBUG") or (os.environ.get("ASVD_STRICT") == "1" and n >= 64):
         lowrank_check(work)
-    return y
 
 
 def fro_norm_sq(w):
@@ -656,6 +662,50 @@ def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0):
             return y
         L.check(lib.asvd_wb_linear_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
                                        bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_wb_linear_f16")
+    return y
+
+
+def lowrank_packed_work(T, r, device):
+    """a zeroed workspace of asvd_lowrank_packed_f16 for up to T tokens at rank r: the barrier words (which must start at zero) and the intermediate"""
+    return torch.zeros(int(L.load().asvd_lowrank_packed_work_bytes(int(T), int(r))), dtype=torch.uint8, device=device)
+
+
+def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_zero, bits, bias, work, group_size=0):
+    """y = fp16(fp16(x wB^T) wA^T + bias) for a pair of packed factors in one launch (K16, asvd_lowrank_packed_f16): the bits of w8_linear /
+    wb_linear applied twice.  x2d [T <= 256, K] fp16 contiguous; bits is the STORAGE width of both factors: 8 (B_codes [r, K], A_codes [N, r]
+    uint8, one code per byte) or 6 / 4 (bitstream rows [r, wb_row_bytes(K, bits)], [N, wb_row_bytes(r, bits)]); scale / zero fp32 [r] and [N],
+    or with group_size 64 / 128 [r, ceil(K / G)] and [N, ceil(r / G)]; bias [N] fp16 or None; K % 16 == 0 and r % 16 == 0, x and the code rows
+    16-byte aligned; work from lowrank_packed_work(>= T, r), one per stream in flight."""
+    lib = L.load(True)
+    group, bits = _group(group_size), int(bits)
+    _dev(x2d, "x")
+    if bits not in (8, 6, 4):
+        raise ValueError(f"lowrank_packed_forward: storage width 8, 6 or 4 bits (got {bits})")
+    if x2d.dim() != 2 or x2d.dtype != torch.float16 or not x2d.is_contiguous() or any(
+            c.dim() != 2 or c.dtype != torch.uint8 or c.stride(1) != 1 for c in (B_codes, A_codes)):
+        raise ValueError("lowrank_packed_forward needs x [T, K] fp16 contiguous and uint8 code matrices with unit column stride")
+    T, K = x2d.shape
+    r, N = B_codes.shape[0], A_codes.shape[0]
+    wB, wA = (K, r) if bits == 8 else (wb_row_bytes(K, bits) if K > 0 else -1, wb_row_bytes(r, bits))
+    if K % 16 or r % 16 or B_codes.shape[1] != wB or A_codes.shape[1] != wA or not 1 <= T <= W8_MAX_TOKENS:
+        raise ValueError(f"lowrank_packed_forward: x {tuple(x2d.shape)} against B {tuple(B_codes.shape)} and A {tuple(A_codes.shape)} at {bits} bits; "
+                         f"K % 16 == 0, r % 16 == 0, 1 <= tokens <= {W8_MAX_TOKENS}")
+    dev = x2d.device
+    _check_params("lowrank_packed_forward (B)", B_scale, B_zero, r, K, group, dev)
+    _check_params("lowrank_packed_forward (A)", A_scale, A_zero, N, r, group, dev)
+    if bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
+        raise ValueError("lowrank_packed_forward needs bias [N] fp16 contiguous on the device of x (or None)")
+    if B_codes.device != dev or A_codes.device != dev or work.device != dev:
+        raise ValueError("lowrank_packed_forward: all tensors must live on the device of x")
+    if x2d.data_ptr() % 16 or B_codes.data_ptr() % 16 or A_codes.data_ptr() % 16 or B_codes.stride(0) % 16 or A_codes.stride(0) % 16:
+        raise ValueError("lowrank_packed_forward needs x and the code rows 16-byte aligned")
+    y = torch.empty((T, N), dtype=torch.float16, device=dev)
+    with _on(dev):
+        L.check(lib.asvd_lowrank_packed_f16(x2d.data_ptr(), T, B_codes.data_ptr(), B_codes.stride(0), B_scale.data_ptr(), B_zero.data_ptr(),
+                                            A_codes.data_ptr(), A_codes.stride(0), A_scale.data_ptr(), A_zero.data_ptr(), bits, group,
+                                            bias.data_ptr() if bias is not None else None, N, K, r, y.data_ptr(), work.data_ptr(), work.numel(),
+                                            _stream(x2d)), "asvd_lowrank_packed_f16")
+    _lowrank_count(work)   # the give-up word of the workspace: as lowrank_forward
     return y
 
 

@@ -297,7 +297,7 @@ int asvd_rtn_quant_batched(int batch, const void* const* w_host, const int* dtyp
  *   [N] fp32;  bias [N] fp16 or NULL;  y [T, N] fp16 contiguous;  any K >= 1, any N >= 1.  Rows are streamed with 16-byte loads when x and q are
  *   16-byte aligned, K % 8 == 0 and ldq % 16 == 0 (element loads for the last K % 16 codes, and throughout otherwise).  The element-load form is correct but slow (measured 3.3-3.7x the time
  *   of an fp16 GEMM at K = 1843): callers that care about speed send such layers through asvd_w8_dequant + their GEMM.  x, y and bias must be 2-byte aligned.
- *   An SVDLinear with packed factors is two calls (z, then y).  Asynchronous.
+ *   An SVDLinear with packed factors is two calls (z, then y), or one of K16.  Asynchronous.
  * asvd_w8_dequant:  out [rows, cols] (ldo) in out_dtype (F32 / F16 / BF16) from q [rows, ldq], scale, zero [rows].  Asynchronous.
  * Bad arguments (NULL, T out of range, ldq < K, misaligned x / y / out) return ASVD_E_BADARG before any device call. */
 #define ASVD_W8_MAX_TOKENS 256
@@ -380,6 +380,28 @@ int asvd_rtn_quant_mse_batched(int batch, const void* const* w_host, const int* 
                                const int64_t* ldw_host, int bits, void* const* out_host, const int64_t* ldo_host, float* const* scale_host,
                                float* const* zero_host, void* const* codes_host, int* flags, void* stream, int64_t group, float norm, int grid,
                                float maxshrink);
+
+/* ---------------------------------------------------------------------------------------------
+ * K16  A packed SVDLinear factor pair (K12 - K14 codes on both factors) in ONE launch, for decode-sized inputs:
+ *        z[T, r] = fp16( x[T, K] . wB^T )      y[T, N] = fp16( z . wA^T + bias )
+ *   with wB / wA dequantized in registers as in K12 - K14.  One persistent launch of at most one workgroup per CU: phase 1 (z), the in-kernel
+ *   grid barrier of K10, phase 2 (y).  Both phases run the tile routine of asvd_w8_linear*_f16 / asvd_wb_linear*_f16, so the result has the
+ *   BITS of those two calls (z, then y) on the same buffers.  It reads the factors' own code / scale / zero buffers: no padded copies.
+ *   x [T, K] fp16 contiguous, 1 <= T <= ASVD_W8_MAX_TOKENS;  K % 16 == 0, r % 16 == 0;  y [T, N] fp16 contiguous;  bias [N] fp16 or NULL.
+ *   bits: the STORAGE width of both factors: 8 (one code per byte, ld >= columns), 6 or 4 (bitstream64 rows, ld >= asvd_wb_row_bytes).
+ *   qB: r rows of K codes, ldB bytes apart;  qA: N rows of r codes, ldA bytes apart.  group: 0 (scaleB, zeroB [r]; scaleA, zeroA [N]) or
+ *   64 / 128 ([r, ceil(K / group)]; [N, ceil(r / group)]), the same for both factors.  x, qB, qA and work 16-byte aligned, ldB and ldA
+ *   multiples of 16, y and bias 2-byte aligned.
+ *   work: asvd_lowrank_packed_work_bytes(T, r) = 256 + round_up(T, 32) * r * 2 bytes (a host-side query), whose first 256 bytes the caller
+ *   zeroes ONCE (barrier state, reusable; the rest needs no initialisation); one `work` must not be used by two launches in flight at the same
+ *   time.  As in K10 the launch assumes its workgroups co-resident; one that waits too long at the barrier sets word 2 of `work` (sticky, the
+ *   host clears it) and every workgroup then overwrites what it stored of y with NaN: such a launch never hangs and never returns numbers.
+ *   Asynchronous.  Bad arguments (NULL other than bias, T out of range, other widths or group sizes, K % 16 or r % 16 != 0, short or
+ *   misaligned leading dimensions, misaligned pointers) return ASVD_E_BADARG, a short workspace ASVD_E_WORKSPACE, before any device call. */
+size_t asvd_lowrank_packed_work_bytes(int64_t T, int64_t r);
+int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB, const void* qA,
+                            int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias, int64_t N,
+                            int64_t K, int64_t r, void* y, void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over

@@ -20,7 +20,13 @@ timed in the same alternation and reported under "bitpacked" with the columns of
   (d) the modules of the narrowest path above ((c) with --code_bits 6 | 4, else (b)) on the SAME code buffers with group-wise scales and zeros
       (csrc/w8_linear.hip, K14; every group of a row carries the row's pair, so (d) stands for the same weights and must give that path's bits),
 timed in the same alternation and reported under "grouped": its time over the per-row pass of the same width, the share of weight-side bytes the
-[N, ng] parameters add (8 / (G bits / 8) per code byte) and whether the slowdown stays within that share plus the per-row pass's own spread."""
+[N, ng] parameters add (8 / (G bits / 8) per code byte) and whether the slowdown stays within that share plus the per-row pass's own spread.
+--fused_pair runs the ASVD shape set only and adds
+  (e) every factor pair of the narrowest path above ((d), else (c), else (b)) through ONE launch (csrc/w8_linear.hip, K16: SVDLinear with
+      fused_packed on the same modules, so on the same code buffers; it must give that path's bits),
+timed in the same alternation, eager and graph replay (the per-stream workspaces are created by a warm-up pass on the capture stream, before
+capture), and reported under "fused_pair": `fused_over_two_launch`, its time over the two-launch pass of the same modules, and whether it is faster
+than that pass by more than the pass's own spread (max - min), the noise floor of the comparison."""
 import argparse
 import json
 import os
@@ -34,13 +40,22 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from asvd4llm_amd import _lib as L  # noqa: E402
 from asvd4llm_amd import ops  # noqa: E402
 from asvd4llm_amd.modules import w8_linear as W  # noqa: E402
+from asvd4llm_amd.modules import svd_linear as S  # noqa: E402
 from asvd4llm_amd.modules import wb_linear as WB  # noqa: E402
 from bench_rtn import HBM_SPEC, median, shape_sets  # noqa: E402
 
 TOKENS = (1, 4, 16, 64)
 
 
-def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0):
+def fused_pair_of(b_mod, a_mod):
+    """an SVDLinear around two packed modules, with the one-launch forward switched on"""
+    m = S.SVDLinear.__new__(S.SVDLinear)
+    nn.Module.__init__(m)
+    m.BLinear, m.ALinear, m.truncation_rank, m.fused_packed = b_mod, a_mod, b_mod.out_features, True
+    return m
+
+
+def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0, fused_pair=False):
     """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear[, WBLinear]) stages applied in order (BLinear, ALinear for a
     factored layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
     g = torch.Generator(device=dev).manual_seed(seed)
@@ -62,6 +77,10 @@ def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0):
                 stage += ((WB.WBLinear.from_bits(stage[2].qbits, q.shape[1], gs, gz, None, bits, torch.float16, group_size=group),) if bitpacked
                           else (W.W8Linear.from_codes(q, gs, gz, None, bits, torch.float16, group_size=group),))
             stages.append(stage)
+        if fused_pair and factored:   # path (e) sits in the BLinear stage and maps x to y; the ALinear stage passes it on
+            for i in range(0, len(stages), 2):
+                stages[i + 1] += (fused_pair_of(stages[i + 1][-1], stages[i][-1]),)
+                stages[i] += (nn.Identity(),)
         out.append([[stages[i + 1], stages[i]] for i in range(0, len(stages), 2)] if factored else [[s] for s in stages])
     return out
 
@@ -80,9 +99,15 @@ def timed_paths(layers, xs, iters, warmup, graph, npaths=2):
     times = [[] for _ in range(npaths)]
     if graph:   # one pass of each path, captured once (a linear chain of launches) and replayed
         run = []
+        cap = torch.cuda.Stream()   # what a path creates per stream on first use (the workspaces of the fused pair) exists before capture
+        cap.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(cap):
+            for which in range(npaths):
+                run_pass(layers, xs, which)
+        torch.cuda.current_stream().wait_stream(cap)
         for which in range(npaths):
             gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
+            with torch.cuda.graph(gr, stream=cap):
                 run_pass(layers, xs, which)
             run.append(gr.replay)
     else:
@@ -119,9 +144,12 @@ def stats(ts):
 
 def run_set(blocks, factored, args, dev):
     bitpacked = args.code_bits != 8
-    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size)
+    fused = bool(args.fused_pair and factored)
+    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size, fused)
     base_path = 2 if bitpacked else 1                       # the per-row pass (d) is compared with
-    npaths = 2 + bitpacked + bool(args.group_size)
+    npaths = 2 + bitpacked + bool(args.group_size) + fused
+    grp_path = 1 + bitpacked + bool(args.group_size)        # (d) when it runs
+    two_path = npaths - 2                                   # the two-launch pass of the modules (e) fuses
     stages = [s for blk in layers for layer in blk for s in layer]
     code_bytes = sum(s[1].qweight.numel() + 8 * s[1].out_features for s in stages)
     fp16_bytes = sum(2 * s[0].weight.numel() for s in stages)
@@ -131,7 +159,7 @@ def run_set(blocks, factored, args, dev):
         res["bitpacked_weight_bytes"] = bit_bytes
     if args.group_size:
         base_bytes = bit_bytes if bitpacked else code_bytes
-        grp_bytes = sum(s[-1].scales.numel() * 8 - 8 * s[-1].out_features for s in stages) + base_bytes
+        grp_bytes = sum(s[grp_path].scales.numel() * 8 - 8 * s[grp_path].out_features for s in stages) + base_bytes
         res.update({"grouped_weight_bytes": grp_bytes, "grouped_extra_byte_share": round(grp_bytes / base_bytes - 1, 4)})
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
     for T in args.tokens:
@@ -162,17 +190,27 @@ def run_set(blocks, factored, args, dev):
                                   "bitpacked_gbps": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / 1e9, 1),
                                   "bitpacked_frac_of_hbm_spec": round((bit_bytes + act_bytes) / (c["median_ms"] * 1e-3) / HBM_SPEC, 4)})
             if args.group_size:   # against the per-row pass of the same width on the same codes; that pass's spread is the noise floor
-                base, d = stats(times[base_path]), stats(times[-1])
+                base, d = stats(times[base_path]), stats(times[grp_path])
                 share = grp_bytes / base_bytes - 1
                 rec[mode].update({"grouped": d, "grouped_over_per_row": round(d["median_ms"] / base["median_ms"], 4),
                                   "grouped_minus_per_row_ms": round(d["median_ms"] - base["median_ms"], 4),
                                   "grouped_within_byte_share_plus_spread": d["median_ms"] <= base["median_ms"] * (1 + share) + base["spread_ms"],
                                   "grouped_gbps": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / 1e9, 1),
                                   "grouped_frac_of_hbm_spec": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / HBM_SPEC, 4)})
+            if fused:   # against the two launches per pair of the same modules; that pass's spread is the noise floor
+                two, e = stats(times[two_path]), stats(times[-1])
+                rec[mode].update({"fused_pair": e, "two_launch": two, "fused_over_two_launch": round(e["median_ms"] / two["median_ms"], 4),
+                                  "fused_minus_two_launch_ms": round(e["median_ms"] - two["median_ms"], 4),
+                                  "two_launch_spread_ms": two["spread_ms"],
+                                  "fused_faster_by_more_than_spread": e["median_ms"] < two["median_ms"] - two["spread_ms"]})
         if args.group_size:
-            diff_d, _ = max_difference(layers, xs, npaths - 1)
-            same_bits = all(torch.equal(run_pass([[layer]], xs, npaths - 1), run_pass([[layer]], xs, base_path)) for layer in layers[0])
+            diff_d, _ = max_difference(layers, xs, grp_path)
+            same_bits = all(torch.equal(run_pass([[layer]], xs, grp_path), run_pass([[layer]], xs, base_path)) for layer in layers[0])
             rec.update({"grouped_max_rel_diff": diff_d / top if top else 0.0, "grouped_bits_equal_per_row_block0": same_bits})
+        if fused:
+            rec["fused_pair_dispatched"] = all(layer[0][-1].fused_packed_refusal(xs[layer[0][0].in_features]) is None for blk in layers for layer in blk)
+            rec["fused_pair_bits_equal_two_launch"] = all(torch.equal(run_pass([[layer]], xs, npaths - 1), run_pass([[layer]], xs, two_path))
+                                                          for blk in layers for layer in blk)
         res["tokens"][str(T)] = rec
     return res
 
@@ -184,6 +222,8 @@ def main():
                     help="6 / 4: quantize to that width (overrides --bits) and add path (c), WBLinear on the codes stored at their own width")
     ap.add_argument("--group_size", type=int, default=0, choices=[0, 64, 128],
                     help="64 / 128: add path (d), the narrowest packed path on the same codes with group-wise scales and zeros")
+    ap.add_argument("--fused_pair", action="store_true",
+                    help="ASVD shape set only: add path (e), every factor pair of the narrowest packed path in one launch (K16), next to its two launches")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=233)
@@ -197,6 +237,8 @@ def main():
         args.bits = args.code_bits
         if args.force_kernel and args.rank_align % 16:
             ap.error("--force_kernel with --code_bits 6 / 4 needs --rank_align to be a multiple of 16: the bit-packed kernel takes K % 16 == 0 only")
+    if args.fused_pair and args.rank_align % 16:
+        ap.error("--fused_pair needs --rank_align to be a multiple of 16: the fused pair takes K % 16 == 0 and r % 16 == 0 only")
     if args.group_size and args.force_kernel and args.rank_align % 16:
         ap.error("--force_kernel with --group_size needs --rank_align to be a multiple of 16: the grouped kernels take K % 16 == 0 only")
     L.load(require_device=True)
@@ -205,13 +247,18 @@ def main():
         W.W8_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
         W.W8Linear.kernel_rows_ok = lambda self: True   # rows that allow no 16-byte loads too (--rank_align 1)
         WB.WB_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
+        S.FUSED_PACKED_MAX_TOKENS = ops.W8_MAX_TOKENS
     res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
            "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
     if args.group_size:
         res["group_size"] = args.group_size
     if args.code_bits != 8:
         res.update({"code_bits": args.code_bits, "bitpacked_dispatch_max_tokens": WB.WB_FORWARD_MAX_TOKENS})
+    if args.fused_pair:
+        res.update({"fused_pair": True, "fused_pair_dispatch_max_tokens": S.FUSED_PACKED_MAX_TOKENS})
     for name, blocks in shape_sets(0.9, args.rank_align).items():
+        if args.fused_pair and "asvd" not in name:
+            continue
         res["sets"][name] = run_set(blocks, "asvd" in name, args, dev)
         torch.cuda.empty_cache()
     print(json.dumps(res), flush=True)
