@@ -67,6 +67,8 @@ SIGNATURES = {
     "asvd_wb_linear_grouped_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "asvd_lowrank_packed_work_bytes": (_sz, [_i64, _i64]),
     "asvd_lowrank_packed_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "asvd_packed_gemm_max_tokens": (_i64, []),
+    "asvd_packed_gemm_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "asvd_fro_worksize": (_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

@@ -29,6 +29,9 @@
 // owns in an iteration (k = 128 it + 64 g .. + 63) lie in ONE group, (128 it + 64 g) >> log2 G, so the lane loads one scale and one zero per
 // iteration, next to its code loads, and everything else is the loop above: the same tiles, the same k split, the same order of every sum.
 //
+// K17, inputs beyond decode (asvd_packed_gemm_f16): the same weight and the same operands on a token-tiled GEMM that stages x through LDS once per
+// workgroup and dequantizes a lane's codes once per up to 128 tokens; its description stands with packed_gemm_kernel below.
+//
 // Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
 // with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
 #include "common.h"
@@ -334,6 +337,175 @@ __global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uin
         }
 }
 
+// ---- K17: a token-tiled GEMM on the packed codes, for inputs beyond decode ---------------------------------------------------------------
+// A workgroup owns BM = 32 MS tokens x BN = 32 MS features of y, MS = 4, 2 or 1 (pg_sub_tiles picks the widest that still fills the chip).  Its
+// four waves are MS feature groups (a wave owns 32 WHOLE features) times WGK = 4 / MS k groups: wave (wn, kg) takes the k steps of 128 with
+// step % WGK == kg.  Per "super-step" of WGK steps the workgroup stages x[BM, 128 WGK] ONCE through LDS (always 128 LDS rows of 256 bytes =
+// 32 KB: row kg BM + r holds token r's 128 values of k group kg), plain 16-byte loads in full 256-byte row segments and ds_write_b128, two
+// buffers: the loads of super-step s + 1 are in flight under the MFMAs of s, one barrier per super-step.  Codes do not go through LDS: lane
+// (i, g) loads row i's 64-code block of its step with the loads of w8_iter_load, dequantizes it ONCE (w8_chunk_f16: the fake quantizer's value)
+// and reuses the eight operands for the MS 32-token sub-tiles, whose x operands it reads from LDS (ds_read_b128); both operands carry the
+// k permutation of the decode kernel (chunk m of the lane's block to MFMAs 2 m, 2 m + 1).
+// LDS image: 16-byte slot c of LDS row R sits at slot c ^ (R & 15).  A ds_read_b128 is served in groups of 16 lanes that here hold 16 rows
+// with pairwise different R & 15 and one column c: unswizzled that is one 4-bank column (16-way conflict), swizzled 16 different slots.
+// Edges: token rows at or beyond T and feature rows at or beyond N re-read the last valid row and are not stored; beyond K BOTH operands are
+// zero (x slots are staged as zeros, code chunks are masked), and a step that lies wholly beyond K is skipped.
+// Order of the sums: a wave adds its steps in ascending k; the WGK partial tiles are added in ascending kg through LDS (the staging buffers,
+// free after the last barrier), by the kg = 0 wave, which adds the bias and stores.  No atomics; nothing depends on timing.
+constexpr int PG_LDS_ROWS = 128;                     // LDS rows (256 bytes: 128 fp16) of one staged x tile
+constexpr int PG_TILE_SLOTS = PG_LDS_ROWS * 16;      // 16-byte slots of one tile
+constexpr int PG_STAGE = PG_TILE_SLOTS / W8_THREADS; // slots a thread stages per super-step
+
+// the lane's 64-code block of step `it` and, GROUPED, its scale and zero.  whole: the step lies within K (unconditional loads)
+template <int BITS, bool GROUPED>
+__device__ __forceinline__ void pg_load_codes(uint4 (&cv)[W8_CW<BITS>], float& sc, float& zr, const uint8_t* __restrict__ qrow,
+                                              const float* __restrict__ srow, const float* __restrict__ zrow, int it, int g, int K, int ng, int gshift,
+                                              bool whole) {
+    const uint4* cp = (const uint4*)(qrow + (int64_t)it * (W8_KIT * BITS / 8));
+    const int k0 = it * W8_KIT + 64 * g;
+    if (whole) {
+#pragma unroll
+        for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cp[m];
+        if constexpr (GROUPED) sc = srow[k0 >> gshift], zr = zrow[k0 >> gshift];
+    } else {
+        // BITS 8: 16-byte word m is chunk m, there when it starts below K (K % 16 == 0).  BITS 6, 4: rows are padded to whole blocks
+#pragma unroll
+        for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = (BITS == 8 ? k0 + 16 * m : k0) < K ? cp[m] : make_uint4(0, 0, 0, 0);
+        if constexpr (GROUPED) {   // a block that starts at or beyond K has no group: the row's last pair, every chunk of it is masked
+            const int gi = min(k0 >> gshift, ng - 1);
+            sc = srow[gi], zr = zrow[gi];
+        }
+    }
+}
+
+// one step of a wave: dequantize the lane's block, and for each of the MS token sub-tiles the 8 MFMAs on the x operands of LDS rows
+// row0 + 32 s + i (row0 = kg BM).  MASK: the step crosses K, chunks at or beyond K are zero
+template <int BITS, int MS, bool MASK>
+__device__ __forceinline__ void pg_step(f32x16 (&acc)[MS], const uint4 (&cv)[W8_CW<BITS>], float sc, float zr, const uint4* __restrict__ tile, int row0,
+                                        int i, int g, int kleft /* K - first k of the lane's block */) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        uint32_t w[W8_CW<BITS>];
+        uint4 w0, w1;
+        w8_chunk_words<BITS>(cv, m, w);
+        w8_chunk_f16<BITS, MASK>(w, sc, zr, MASK ? max(0, min(16, kleft - 16 * m)) : 16, w0, w1);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int s = 0; s < MS; ++s) {
+                const uint4 xa = tile[(row0 + 32 * s + i) * 16 + ((8 * g + 2 * m + h) ^ (i & 15))];
+                acc[s] = w8_mfma(xa, h ? w1 : w0, acc[s]);
+            }
+    }
+}
+
+template <int BITS, bool GROUPED, int MS>
+__global__ __launch_bounds__(W8_THREADS, 2) void packed_gemm_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
+                                                                   const float* __restrict__ scale, const float* __restrict__ zero,
+                                                                   const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ng,
+                                                                   int gshift) {
+    constexpr int WGK = W8_WAVES / MS, BM = 32 * MS, BN = 32 * MS;
+    __shared__ uint4 lds[2 * PG_TILE_SLOTS];   // ALL the LDS of the kernel: the two x tiles, then the partial tiles of the k groups (64 KB)
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int i = lane & 31, g = lane >> 5;
+    const int wn = wave % MS, kg = wave / MS;
+    const int t0 = blockIdx.y * BM, n0 = blockIdx.x * BN + 32 * wn;
+    const int wrow = min(n0 + i, N - 1);
+    const uint8_t* qrow = q + (int64_t)wrow * ldq + 8 * BITS * g;
+    const float* srow = scale + (GROUPED ? (int64_t)wrow * ng : 0);
+    const float* zrow = zero + (GROUPED ? (int64_t)wrow * ng : 0);
+    float sc = 0.f, zr = 0.f, scn = 0.f, zrn = 0.f;
+    if constexpr (!GROUPED) sc = scn = scale[wrow], zr = zrn = zero[wrow];
+
+    // staging: slot p of the thread is LDS row 16 p + (tid >> 4), column slot tid & 15: 16 threads take one row's 256 bytes
+    const int srw = tid >> 4, scol = tid & 15;
+    const uint16_t* xsrc[PG_STAGE];   // token row (clamped) and column of every slot, at k group 0 of super-step 0
+    int skoff[PG_STAGE];              // first k of the slot within a super-step
+#pragma unroll
+    for (int p = 0; p < PG_STAGE; ++p) {
+        const int R = 16 * p + srw, r = R % BM;
+        skoff[p] = (R / BM) * W8_KIT + 8 * scol;
+        xsrc[p] = x + (int64_t)min(t0 + r, T - 1) * K + skoff[p];
+    }
+    const int sdst = srw * 16 + (scol ^ srw);   // (16 p + srw) & 15 == srw
+
+    const int nk = (K + W8_KIT - 1) / W8_KIT, nss = (nk + WGK - 1) / WGK;
+    f32x16 acc[MS];
+#pragma unroll
+    for (int s = 0; s < MS; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+
+    uint4 xs[PG_STAGE], cv[W8_CW<BITS>], cvn[W8_CW<BITS>];
+#pragma unroll
+    for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cvn[m] = make_uint4(0, 0, 0, 0);
+    auto stage_load = [&](int ss) {
+        const int kb = ss * (WGK * W8_KIT);
+        if (kb + WGK * W8_KIT <= K) {   // the whole super-step lies within K: unconditional loads (workgroup-uniform)
+#pragma unroll
+            for (int p = 0; p < PG_STAGE; ++p) xs[p] = *(const uint4*)(xsrc[p] + kb);
+        } else {
+#pragma unroll
+            for (int p = 0; p < PG_STAGE; ++p) xs[p] = kb + skoff[p] < K ? *(const uint4*)(xsrc[p] + kb) : make_uint4(0, 0, 0, 0);   // K % 8 == 0
+        }
+    };
+    auto stage_write = [&](int buf) {
+#pragma unroll
+        for (int p = 0; p < PG_STAGE; ++p) lds[buf * PG_TILE_SLOTS + 256 * p + sdst] = xs[p];
+    };
+
+    stage_load(0);
+    if (kg < nk) pg_load_codes<BITS, GROUPED>(cv, sc, zr, qrow, srow, zrow, kg, g, K, ng, gshift, (kg + 1) * W8_KIT <= K);
+    stage_write(0);
+    __syncthreads();
+    for (int ss = 0; ss < nss; ++ss) {
+        const int it = ss * WGK + kg, itn = it + WGK;
+        if (ss + 1 < nss) stage_load(ss + 1);
+        if (itn < nk) pg_load_codes<BITS, GROUPED>(cvn, scn, zrn, qrow, srow, zrow, itn, g, K, ng, gshift, (itn + 1) * W8_KIT <= K);
+        const uint4* tile = lds + (ss & 1) * PG_TILE_SLOTS;
+        if ((it + 1) * W8_KIT <= K) pg_step<BITS, MS, false>(acc, cv, sc, zr, tile, kg * BM, i, g, 64);
+        else if (it < nk) pg_step<BITS, MS, true>(acc, cv, sc, zr, tile, kg * BM, i, g, K - it * W8_KIT - 64 * g);
+        if (ss + 1 < nss) stage_write((ss + 1) & 1);   // the buffer of super-step ss - 1: every wave has passed the barrier that ended it
+#pragma unroll
+        for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cvn[m];
+        if constexpr (GROUPED) sc = scn, zr = zrn;
+        __syncthreads();
+    }
+
+    if constexpr (WGK > 1) {   // the partial tiles of k groups 1 .. WGK - 1, added in that order by the k group 0 wave of the same features
+        float* red = (float*)lds;
+        if (kg > 0) {
+#pragma unroll
+            for (int s = 0; s < MS; ++s)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) red[((((kg - 1) * MS + wn) * MS + s) * 16 + r) * 64 + lane] = acc[s][r];
+        }
+        __syncthreads();
+        if (kg == 0) {
+#pragma unroll
+            for (int k2 = 1; k2 < WGK; ++k2)
+#pragma unroll
+                for (int s = 0; s < MS; ++s)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[s][r] += red[((((k2 - 1) * MS + wn) * MS + s) * 16 + r) * 64 + lane];
+        }
+    }
+    if (kg == 0 && n0 + i < N) {   // accumulator register r of lane (i, g): token (r & 3) + 8 (r >> 2) + 4 g of the sub-tile, feature i
+        const float b = bias ? f16_bits_to_f32(bias[n0 + i]) : 0.f;
+#pragma unroll
+        for (int s = 0; s < MS; ++s)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int tok = t0 + 32 * s + (r & 3) + 8 * (r >> 2) + 4 * g;
+                if (tok < T) {
+                    float v = acc[s][r];
+                    if (bias) v += b;
+                    y[(int64_t)tok * N + n0 + i] = f32_to_f16_bits(v);
+                }
+            }
+    }
+}
+
 // ---- dequantization to a dense weight ---------------------------------------------------------------------------------------------
 // scale / zero are [rows, ng], a group is 1 << gshift columns (per row: ng = 1 and W8_ROW_SHIFT, which sends every column to group 0).  A
 // thread's 16 codes start at a multiple of 16 and so share one group
@@ -588,6 +760,26 @@ void lowrank_packed_go(int grid, hipStream_t stream, const void* x, int64_t T, c
                        (uint16_t*)y, (uint16_t*)((char*)work + 256), (unsigned*)work, ft1, ft2, gshift);
 }
 
+// K17: the widest tile (32 MS tokens x 32 MS features, MS = 4, 2, 1) that the token count fills and that still puts a workgroup on every
+// other CU; below that the tile narrows and the k steps spread over the 4 / MS wave groups of more workgroups instead
+int pg_sub_tiles(int64_t T, int64_t N, int cus) {
+    for (int ms = 4; ms > 1; ms /= 2)
+        if (T > 16 * ms && ceil_div64(T, 32 * ms) * ceil_div64(N, 32 * ms) * 2 >= cus) return ms;
+    return 1;
+}
+
+template <int BITS, bool GROUPED>
+void pg_go(int ms, hipStream_t stream, const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias,
+           int64_t N, int64_t K, void* y, int ng, int gshift) {
+    const dim3 grid((unsigned)ceil_div64(N, 32 * ms), (unsigned)ceil_div64(T, 32 * ms));
+#define ASVD_PG_LAUNCH(MS) hipLaunchKernelGGL((packed_gemm_kernel<BITS, GROUPED, MS>), grid, dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T, \
+                                              (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ng, gshift)
+    if (ms == 4) ASVD_PG_LAUNCH(4);
+    else if (ms == 2) ASVD_PG_LAUNCH(2);
+    else ASVD_PG_LAUNCH(1);
+#undef ASVD_PG_LAUNCH
+}
+
 }  // namespace
 
 extern "C" {
@@ -692,6 +884,35 @@ int asvd_wb_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t 
                                int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream) {
     if (group != 64 && group != 128) return ASVD_E_BADARG;
     return wb_linear_launch(x, T, q, ld_bytes, bits, scale, zero, (int)group, bias, N, K, y, stream);
+}
+
+int64_t asvd_packed_gemm_max_tokens(void) { return ASVD_PACKED_GEMM_MAX_TOKENS; }
+
+int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group,
+                         const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (!x || !q || !scale || !zero || !y) return ASVD_E_BADARG;
+    if ((bits != 8 && bits != 6 && bits != 4) || (group != 0 && group != 64 && group != 128)) return ASVD_E_BADARG;
+    if (T < 1 || T > ASVD_PACKED_GEMM_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 128 || K > 0x7fffffff - 512) return ASVD_E_BADARG;
+    if (ld_bytes < (bits == 8 ? K : wb_row_bytes(K, bits)) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    int cus = 0;
+    const int st = w8_cu_count(&cus);
+    if (st != ASVD_OK) return st;
+    const int ms = pg_sub_tiles(T, N, cus);
+    const int ng = group ? (int)ceil_div64(K, group) : 1, gshift = group == 64 ? 6 : 7;
+#define ASVD_PG_GO(B, GR) pg_go<B, GR>(ms, (hipStream_t)stream, x, T, q, ld_bytes, scale, zero, bias, N, K, y, ng, gshift)
+    if (group) {
+        if (bits == 8) ASVD_PG_GO(8, true);
+        else if (bits == 6) ASVD_PG_GO(6, true);
+        else ASVD_PG_GO(4, true);
+    } else {
+        if (bits == 8) ASVD_PG_GO(8, false);
+        else if (bits == 6) ASVD_PG_GO(6, false);
+        else ASVD_PG_GO(4, false);
+    }
+#undef ASVD_PG_GO
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
 }
 
 }  // extern "C"

@@ -1,9 +1,27 @@
 """What the packed Linear modules (w8_linear.W8Linear: one code per byte; wb_linear.WBLinear: codes at their own width) have in common: the
 protection of the buffers that define the weight against dtype casts of the model, the conditions under which forward() takes a kernel, and
 the dequantize + F.linear path every other input takes."""
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+# Token count up to which an input beyond decode size takes the token-tiled GEMM on the codes (K17, csrc/w8_linear.hip: ops.packed_gemm) once it
+# is switched on (packed_gemm_enabled): the largest measured token count at which that kernel is no slower than dequantize + F.linear, the path
+# these inputs take otherwise (tools/bench_w8_forward.py --gemm on MI355X, graph replay, profiles/w8_gemm.json, DESIGN.md section 4 "K17").  On the
+# Llama-2-7B plain set the kernel takes 0.56 / 0.57 / 0.74 / 0.86 of the dense path's time at 32 / 64 / 128 / 256 tokens with byte codes (0.49 /
+# 0.52 / 0.72 / 0.86 with 4-bit rows) and 1.30 / 1.34 at 512 / 2048 (1.42 / 1.36); on the ASVD-0.9 rank_align 128 factor set 0.58 / 0.60 / 0.64 /
+# 0.84, then 1.04 / 1.30.  6-bit rows and group-wise scales (measured on 8 of the 32 blocks) cross between 256 and 512 as well; byte codes with
+# groups of 64 on the plain set are level at 256 (1.007, inside the dense path's spread).  Above the constant the dense path is faster and costs an
+# out x in fp16 temporary per call (90 MB for an 11008 x 4096 layer).
+PACKED_GEMM_MAX_TOKENS = 256
+
+
+def packed_gemm_enabled():
+    """The token-tiled GEMM on the codes is opt-in (ASVD_PACKED_GEMM=1, or `module.packed_gemm = True` on one packed Linear): it avoids the
+    out x in fp16 temporary of dequantize + F.linear; off, every input beyond decode size keeps that path."""
+    return os.environ.get("ASVD_PACKED_GEMM", "0") == "1"
 
 
 class PackedLinear(nn.Module):
@@ -33,6 +51,14 @@ class PackedLinear(nn.Module):
         x2d = x.reshape(-1, x.shape[-1])
         x2d = x2d if x2d.is_contiguous() else x2d.contiguous()
         return x2d if x2d.data_ptr() % 16 == 0 else None
+
+    def _gemm_input(self, x, decode_max_tokens):
+        """x as _kernel_input gives it when it goes to the token-tiled GEMM (K17): switched on, more tokens than the decode kernel takes
+        (`decode_max_tokens`), at most PACKED_GEMM_MAX_TOKENS, and the conditions of _kernel_input; None otherwise"""
+        if not (getattr(self, "packed_gemm", False) or packed_gemm_enabled()):
+            return None
+        x2d = self._kernel_input(x, PACKED_GEMM_MAX_TOKENS)
+        return x2d if x2d is not None and x2d.shape[0] > decode_max_tokens else None
 
     def _dense_forward(self, x):
         w, b = self.dequantize(), self.bias

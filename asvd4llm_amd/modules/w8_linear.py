@@ -3,7 +3,8 @@
 The weight it stands for is  w[n, k] = (scales[n] * (qweight[n, k] - zeros[n])).to(weight_dtype),  the value the fake quantizer
 (quantization.rtn_quant_sequential) writes into an nn.Linear, bit for bit.  Decode-sized fp16 inputs run on the W8A16 kernel of
 csrc/w8_linear.hip, which dequantizes to exactly that value in registers; every other input dequantizes the layer's weight into a temporary
-(csrc/w8_linear.hip as well) and calls F.linear on it, so the model's resident size stays packed.
+(csrc/w8_linear.hip as well) and calls F.linear on it, so the model's resident size stays packed.  Opt-in (ASVD_PACKED_GEMM=1 or `packed_gemm = True`,
+modules/packed_linear.py): fp16 inputs of 17 .. PACKED_GEMM_MAX_TOKENS tokens run on the token-tiled GEMM on the codes instead (K17), without the temporary.
 
 Not an nn.Linear subclass on purpose: collect_linear_info, the calibration hooks and quantization._find_linears select nn.Linear modules and
 must keep ignoring packed ones.
@@ -90,6 +91,10 @@ class W8Linear(PackedLinear):
         x2d = self._kernel_input(x, W8_FORWARD_MAX_TOKENS)
         if x2d is not None:
             y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            return y.view(*x.shape[:-1], self.out_features)
+        x2d = self._gemm_input(x, W8_FORWARD_MAX_TOKENS)   # opt-in (packed_linear.packed_gemm_enabled): the GEMM on the codes, one per byte
+        if x2d is not None:
+            y = ops.packed_gemm(x2d, self.qweight, 8, self.scales, self.zeros, self.bias, group_size=self.group_size)
             return y.view(*x.shape[:-1], self.out_features)
         return self._dense_forward(x)
 

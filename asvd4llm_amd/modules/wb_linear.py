@@ -6,7 +6,8 @@ The weight it stands for is  w[n, k] = (scales[n] * (code[n, k] - zeros[n])).to(
 in bits [bits k, bits (k + 1)) of the row read as one little-endian integer, zero-padded to whole blocks of 64 codes, so a row is
 ceil(in / 64) * 8 * bits bytes (csrc/w8_linear.hip, K13; the on-disk format "bitstream64" of export.py).  Decode-sized fp16 inputs run on the
 kernel that unpacks in registers and gives the bits of the W8A16 kernel on the same codes; every other input dequantizes the layer's weight into
-a temporary and calls F.linear on it.
+a temporary and calls F.linear on it.  Opt-in (ASVD_PACKED_GEMM=1 or `packed_gemm = True`, modules/packed_linear.py): fp16 inputs of 17 ..
+PACKED_GEMM_MAX_TOKENS tokens run on the token-tiled GEMM on the bitstream rows instead (K17), without the temporary.
 
 Neither an nn.Linear nor a W8Linear on purpose: the nn.Linear selections must keep ignoring packed layers and export.packed_layers_of must keep
 telling the two storage forms apart.
@@ -123,6 +124,10 @@ class WBLinear(PackedLinear):
         x2d = self._kernel_input(x, WB_FORWARD_MAX_TOKENS)
         if x2d is not None:
             y = ops.wb_linear(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            return y.view(*x.shape[:-1], self.out_features)
+        x2d = self._gemm_input(x, WB_FORWARD_MAX_TOKENS)   # opt-in (packed_linear.packed_gemm_enabled): the GEMM on the bitstream rows
+        if x2d is not None:
+            y = ops.packed_gemm(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size)
             return y.view(*x.shape[:-1], self.out_features)
         return self._dense_forward(x)
 

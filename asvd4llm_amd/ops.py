@@ -709,6 +709,44 @@ def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_ze
     return y
 
 
+PACKED_GEMM_MAX_TOKENS = 1 << 20  # ASVD_PACKED_GEMM_MAX_TOKENS (asvd_packed_gemm_max_tokens)
+
+
+def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0):
+    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (code - zero)) for inputs beyond decode (K17, asvd_packed_gemm_f16): the token-tiled
+    GEMM that stages x through LDS once per workgroup and streams the codes once per tile of up to 128 tokens.  x2d [T, K] fp16 contiguous,
+    K % 16 == 0, 1 <= T <= PACKED_GEMM_MAX_TOKENS.  bits is the STORAGE width of `codes`: 8 (W8Linear.qweight: [N, K] uint8, unit column
+    stride) or 6 / 4 (WBLinear.qbits: bitstream rows [N, wb_row_bytes(K, bits)]).  scale / zero [N] fp32, or with group_size 64 / 128
+    [N, ceil(K / group_size)]; bias [N] fp16 or None; x2d and the code rows 16-byte aligned.  One launch, deterministic; the weight is the
+    one w8_dequant / wb_dequant write, bit for bit.  Every argument check comes before the device is asked for."""
+    group, bits = _group(group_size), int(bits)
+    if bits not in (8, 6, 4):
+        raise ValueError(f"packed_gemm: storage width 8, 6 or 4 bits (got {bits})")
+    if x2d.dim() != 2 or codes.dim() != 2 or x2d.dtype != torch.float16 or codes.dtype != torch.uint8 or not x2d.is_contiguous() or codes.stride(1) != 1:
+        raise ValueError(f"packed_gemm needs x [T, K] fp16 contiguous and codes [N, row bytes] uint8 with unit column stride (got {tuple(x2d.shape)} "
+                         f"{x2d.dtype}, {tuple(codes.shape)} {codes.dtype})")
+    T, K = x2d.shape
+    N = codes.shape[0]
+    if K < 1 or K % 16 or N < 1 or codes.shape[1] != (K if bits == 8 else wb_row_bytes(K, bits)) or not 1 <= T <= PACKED_GEMM_MAX_TOKENS:
+        raise ValueError(f"packed_gemm: x {tuple(x2d.shape)} against codes {tuple(codes.shape)} at {bits} bits; K % 16 == 0, "
+                         f"1 <= tokens <= {PACKED_GEMM_MAX_TOKENS}")
+    dev = x2d.device
+    _check_params("packed_gemm", scale, zero, N, K, group, dev)
+    if bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
+        raise ValueError("packed_gemm needs bias [N] fp16 contiguous on the device of x (or None)")
+    if codes.device != dev:
+        raise ValueError("packed_gemm: all tensors must live on the device of x")
+    if x2d.data_ptr() % 16 or codes.data_ptr() % 16 or codes.stride(0) % 16:
+        raise ValueError("packed_gemm needs x and the code rows 16-byte aligned")
+    _dev(x2d, "x")
+    lib = L.load(True)
+    y = torch.empty((T, N), dtype=torch.float16, device=dev)
+    with _on(dev):
+        L.check(lib.asvd_packed_gemm_f16(x2d.data_ptr(), T, codes.data_ptr(), codes.stride(0), bits, scale.data_ptr(), zero.data_ptr(), group,
+                                         bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_packed_gemm_f16")
+    return y
+
+
 PROFILE_CLASSES = ["pack", "sgram", "evd", "supdate", "finalize", "snapshot", "gram1", "update1", "supgram"]
 
 

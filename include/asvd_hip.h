@@ -404,6 +404,26 @@ int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ld
                             int64_t K, int64_t r, void* y, void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K17  A token-tiled GEMM on packed RTN codes, for inputs beyond decode (prefill, perplexity windows, batched decode):
+ *        y[T, N] = fp16( x[T, K] . w^T + bias ),   w[n, k] = fp16( scale * (code - zero) )
+ *   ONE entry for what K12 / K13 / K14 cover in four.  w is formed in registers, bit for bit what asvd_w8_dequant / asvd_wb_dequant write (the
+ *   subtraction, one fp32 product, one rounding; the scale never moves behind the accumulation), and goes to the fp16 matrix instruction with
+ *   fp32 accumulation.  A workgroup owns 32 m tokens x 32 m features (m = 4, 2 or 1, chosen from T, N and the CU count), stages its x tile once
+ *   per 128 (4 / m) values of k through LDS for all its waves, and streams each code once per 32 m tokens.  Every sum has a fixed order (no atomics):
+ *   two calls return the same bits; the order depends on (T, N, CU count) only.  A token row depends on its own x row only: beyond T, N and K
+ *   nothing that exists is multiplied by padding, so a NaN / Inf in one token row changes that row only.
+ *   x [T, K] fp16 contiguous, 1 <= T <= ASVD_PACKED_GEMM_MAX_TOKENS (asvd_packed_gemm_max_tokens() returns it);  y [T, N] fp16 contiguous;
+ *   bias [N] fp16 or NULL.  bits: the STORAGE width: 8 (q [N, ld_bytes], one code per byte, ld_bytes >= K) or 6 / 4 (bitstream64 rows of
+ *   asvd_wb_row_bytes(K, bits) bytes, ld_bytes apart).  group: 0 (scale, zero [N]) or 64 / 128 ([N, ceil(K / group)]).  K % 16 == 0;  x and q
+ *   16-byte aligned, ld_bytes a multiple of 16;  y and bias 2-byte aligned.  No workspace.  Asynchronous.
+ *   Bad arguments (NULL other than bias, T out of range, other widths or group sizes, K % 16 != 0, a short or misaligned ld_bytes, misaligned
+ *   pointers) return ASVD_E_BADARG before any device call. */
+#define ASVD_PACKED_GEMM_MAX_TOKENS 1048576
+int64_t asvd_packed_gemm_max_tokens(void);
+int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group,
+                         const void* bias, int64_t N, int64_t K, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

@@ -26,7 +26,14 @@ timed in the same alternation and reported under "grouped": its time over the pe
       fused_packed on the same modules, so on the same code buffers; it must give that path's bits),
 timed in the same alternation, eager and graph replay (the per-stream workspaces are created by a warm-up pass on the capture stream, before
 capture), and reported under "fused_pair": `fused_over_two_launch`, its time over the two-launch pass of the same modules, and whether it is faster
-than that pass by more than the pass's own spread (max - min), the noise floor of the comparison."""
+than that pass by more than the pass's own spread (max - min), the noise floor of the comparison.
+--gemm measures the token-tiled GEMM on the codes (csrc/w8_linear.hip, K17) instead, at --tokens beyond decode size (default 32 .. 2048), on the
+modules of the narrowest path above.  Per shape set and token count it times three passes in alternation, graph replay (device time):
+  (g) the packed GEMM (the modules with packed_gemm on and the dispatch maximum lifted, so every token count takes the kernel),
+  (h) the dense path, dequantize + F.linear (PackedLinear._dense_forward: what the modules do for these inputs with the switch off),
+  (a) nn.Linear on the resident fake-quantized fp16 weights (context only: it keeps two to four times the memory),
+and reports `gemm_over_dense`, whether (g) is not slower than (h) by more than (h)'s spread, (g)'s algorithmic GB/s and TFLOP/s, the largest
+N K 2-byte temporary (h) allocates per layer, and the largest difference of (g) from (a)."""
 import argparse
 import json
 import os
@@ -137,6 +144,86 @@ def max_difference(layers, xs, which=1):
     return worst, top
 
 
+GEMM_TOKENS = (32, 64, 128, 256, 512, 2048)
+
+
+@torch.no_grad()
+def run_pass_fn(layers, xs, fn):
+    for blk in layers:
+        for layer in blk:
+            y = xs[layer[0][0].in_features]
+            for stage in layer:
+                y = fn(stage)(y)
+    return y
+
+
+def timed_graphs(passes, iters, warmup):
+    """every pass captured into a device graph (after one eager run on the capture stream), replayed in alternation, events around each replay"""
+    cap = torch.cuda.Stream()
+    cap.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(cap):
+        for f in passes:
+            f()
+    torch.cuda.current_stream().wait_stream(cap)
+    run = []
+    for f in passes:
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=cap):
+            f()
+        run.append(gr.replay)
+    times = [[] for _ in passes]
+    for it in range(warmup + iters):
+        for r, ts in zip(run, times):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r()
+            e1.record()
+            e1.synchronize()
+            if it >= warmup:
+                ts.append(e0.elapsed_time(e1))
+    return times
+
+
+def run_set_gemm(blocks, factored, args, dev):
+    bitpacked = args.code_bits != 8
+    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size)
+    stages = [s for blk in layers for layer in blk for s in layer]
+    for s in stages:
+        s[-1].packed_gemm = True
+    narrow = [s[-1] for s in stages]
+    code_bytes = sum((m.qbits if bitpacked else m.qweight).numel() + 8 * m.scales.numel() for m in narrow)
+    res = {"launches_per_pass": len(stages), "module": type(narrow[0]).__name__, "storage_bits": args.code_bits, "group_size": args.group_size,
+           "fp16_weight_bytes": sum(2 * s[0].weight.numel() for s in stages), "code_bytes": code_bytes,
+           "largest_dense_temporary_bytes": max(2 * s[0].weight.numel() for s in stages), "tokens": {}}
+    g = torch.Generator(device=dev).manual_seed(args.seed + 1)
+    for T in args.tokens:
+        xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
+        launched, real = [], ops.packed_gemm
+        ops.packed_gemm = lambda *a, **k: (launched.append(1), real(*a, **k))[1]
+        run_pass_fn(layers, xs, lambda s: s[-1])
+        ops.packed_gemm = real
+        assert len(launched) == len(stages), "a module did not dispatch the GEMM"
+        passes = [lambda: run_pass_fn(layers, xs, lambda s: s[-1]), lambda: run_pass_fn(layers, xs, lambda s: s[-1]._dense_forward),
+                  lambda: run_pass_fn(layers, xs, lambda s: s[0])]
+        worst = top = 0.0
+        for layer in layers[0]:
+            ya, yg = run_pass_fn([[layer]], xs, lambda s: s[0]), run_pass_fn([[layer]], xs, lambda s: s[-1])
+            worst, top = max(worst, (ya.float() - yg.float()).abs().max().item()), max(top, ya.float().abs().max().item())
+        tg, td, tf = (stats(t) for t in timed_graphs(passes, args.iters, args.warmup))
+        flops = sum(2.0 * T * s[0].weight.numel() for s in stages)
+        nbytes = code_bytes + sum(2 * T * (s[0].in_features + s[0].out_features) for s in stages)
+        res["tokens"][str(T)] = {"gemm": tg, "dense_path": td, "fp16_linear": tf,
+                                 "gemm_over_dense": round(tg["median_ms"] / td["median_ms"], 4),
+                                 "gemm_over_fp16_linear": round(tg["median_ms"] / tf["median_ms"], 4),
+                                 "gemm_not_slower_than_dense": tg["median_ms"] <= td["median_ms"] + td["spread_ms"],
+                                 "gemm_gbps": round(nbytes / (tg["median_ms"] * 1e-3) / 1e9, 1),
+                                 "gemm_tflops": round(flops / (tg["median_ms"] * 1e-3) / 1e12, 2),
+                                 "dense_tflops": round(flops / (td["median_ms"] * 1e-3) / 1e12, 2),
+                                 "max_rel_diff_block0": worst / top if top else 0.0}
+    del layers
+    return res
+
+
 def stats(ts):
     return {"median_ms": round(median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "spread_ms": round(max(ts) - min(ts), 4),
             "all_ms": [round(t, 4) for t in ts]}
@@ -224,13 +311,20 @@ def main():
                     help="64 / 128: add path (d), the narrowest packed path on the same codes with group-wise scales and zeros")
     ap.add_argument("--fused_pair", action="store_true",
                     help="ASVD shape set only: add path (e), every factor pair of the narrowest packed path in one launch (K16), next to its two launches")
+    ap.add_argument("--gemm", action="store_true",
+                    help="measure the token-tiled GEMM on the codes (K17) against dequantize + F.linear and fp16 nn.Linear at --tokens (default 32 .. 2048)")
+    ap.add_argument("--blocks", type=int, default=0, help="--gemm: decoder blocks per shape set (0: all 32)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=233)
-    ap.add_argument("--tokens", type=lambda v: [int(t) for t in v.split(",")], default=list(TOKENS), help="token counts, comma separated")
+    ap.add_argument("--tokens", type=lambda v: [int(t) for t in v.split(",")], default=None, help="token counts, comma separated")
     ap.add_argument("--rank_align", type=int, default=128, help="rank alignment of the ASVD shape set (1: ranks such as 1843, whose rows allow no 16-byte loads)")
     ap.add_argument("--force_kernel", action="store_true", help="measure the kernel at every token count and for every row alignment, whatever W8Linear.forward dispatches")
     args = ap.parse_args()
+    if args.tokens is None:
+        args.tokens = list(GEMM_TOKENS if args.gemm else TOKENS)
+    if args.gemm and (args.force_kernel or args.fused_pair or args.rank_align % 16):
+        ap.error("--gemm goes without --force_kernel / --fused_pair and needs --rank_align to be a multiple of 16")
     if args.iters < 10:
         ap.error("--iters must be at least 10")
     if args.code_bits != 8:
@@ -248,6 +342,16 @@ def main():
         W.W8Linear.kernel_rows_ok = lambda self: True   # rows that allow no 16-byte loads too (--rank_align 1)
         WB.WB_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
         S.FUSED_PACKED_MAX_TOKENS = ops.W8_MAX_TOKENS
+    if args.gemm:
+        from asvd4llm_amd.modules import packed_linear as P
+        P.PACKED_GEMM_MAX_TOKENS = ops.PACKED_GEMM_MAX_TOKENS   # measure the kernel at every token count, whatever forward() dispatches
+        res = {"metric": "w8_gemm", "bits": args.bits, "iters": args.iters, "warmup": args.warmup, "rank_align": args.rank_align,
+               "timing": "graph replay, device events", "sets": {}}
+        for name, blocks in shape_sets(0.9, args.rank_align).items():
+            res["sets"][name] = run_set_gemm(blocks[:args.blocks] if args.blocks else blocks, "asvd" in name, args, dev)
+            torch.cuda.empty_cache()
+        print(json.dumps(res), flush=True)
+        return
     res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
            "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
     if args.group_size:
