@@ -176,6 +176,10 @@ def build_parser():
     parser.add_argument("--use_bos", action="store_true", help="use bos token in calibration")
     # ---- additive, build-only flags ----
     parser.add_argument("--random_init", action="store_true", help="shape-faithful random-init model named by --model_id (no checkpoints offline)")
+    parser.add_argument("--svd_ortho", action="store_true",
+                        help="re-orthonormalise the long side's singular vectors after every factorisation (K18: U = W V / sigma loses orthogonality on "
+                             "graded spectra, 2e-3 .. 2.5e-2 measured); matters under --sigma_fuse U / V, where one emitted factor is the raw vector "
+                             "matrix.  Off by default; ASVD_SVD_ORTHO=1 is the environment switch of the library")
     parser.add_argument("--exclude_lm_head", action="store_true", help="do not hook/sweep/compress lm_head (the reference includes it)")
     parser.add_argument("--save_repo", type=str, default="", help="write the compressed model in the exported HF-repo layout of the reference (truncation_ranks in config.json)")
     parser.add_argument("--no_fused_sweep", dest="fused_sweep", action="store_false",

@@ -100,6 +100,8 @@ def binary_search_truncation_rank(model, sensitivity_dict, calib_loader, args):
     weights = {name: modules[name].weight.numel() for name in plans.layers}
     rank, ws = parallel.world()
     from_linear_kw = dict(alpha=args.alpha, act_aware=args.act_aware, sigma_fuse=args.sigma_fuse, rank_align=args.rank_align)
+    if getattr(args, "svd_ortho", False):  # additive flag: the keyword travels only when it is set
+        from_linear_kw["ortho"] = True
 
     if args.ppl_target > 0:
         assert ws == 1, "ppl-target search evaluates the whole model per round: replicas only (SURVEY.md §8e)"

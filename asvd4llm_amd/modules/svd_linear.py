@@ -24,6 +24,12 @@ def _strict():
     return os.environ.get("ASVD_STRICT", "0") == "1"
 
 
+def _ortho(ortho):
+    """Re-orthonormalise the long side's singular vectors after the factorisation (K18, ops.reorth_batched)?  OPT-IN: the keyword, or
+    ASVD_SVD_ORTHO=1 when the keyword is None.  Off by default."""
+    return os.environ.get("ASVD_SVD_ORTHO", "0") == "1" if ortho is None else bool(ortho)
+
+
 FUSED_FORWARD_MAX_TOKENS, FUSED_FORWARD_MAX_OUT = 16, 8192  # where the one-launch forward measured faster than two GEMM launches (tokens; in/out features)
 
 
@@ -128,8 +134,8 @@ class SVDLinear(nn.Module):
         return ops.make_scale(scaling, None if fisher is None else fisher.to(dev), alpha=alpha, eps=1e-6)
 
     @staticmethod
-    def _cache_key(linear, act_aware, alpha):
-        """(key, contiguous weight).  Content signature: `.data` edits do not bump Parameter._version, so the values are hashed:
+    def _cache_key(linear, act_aware, alpha, ortho=False):
+        """(key, contiguous weight).  ortho (the resolved setting, _ortho) is part of the key: factors of the two kinds never mix.  Content signature: `.data` edits do not bump Parameter._version, so the values are hashed:
         sum of squares of every element (K8 kernel) AND a position-weighted fp64 checksum over a strided sample of <= 8192 elements
         (sign flips and permutations keep the first and change the second), plus Parameter._version — all read back in ONE host sync."""
         w = linear.weight.data
@@ -155,15 +161,18 @@ class SVDLinear(nn.Module):
         sigs = [_sig(wc), _sig(stat), _sig(fis)]
         vals = torch.stack(pend).tolist()  # the one host sync
         sigs = [None if sg is None else (sg[0], sg[1], vals[sg[2]], vals[sg[2] + 1]) for sg in sigs]
-        key = (w.data_ptr(), int(linear.weight._version), sigs[0], bool(act_aware), float(alpha) if act_aware else None, sigs[1], sigs[2])
+        key = (w.data_ptr(), int(linear.weight._version), sigs[0], bool(act_aware), float(alpha) if act_aware else None, sigs[1], sigs[2], bool(ortho))
         return key, wc
 
     @staticmethod
-    def factorize(linear, act_aware=False, alpha=1, k=None, k_compute=None):
+    def factorize(linear, act_aware=False, alpha=1, k=None, k_compute=None, ortho=None):
         """One exact SVD of W*diag(s) on the device, cached on the module.  Returns (U, S, V, s).
         k: number of leading triplets needed now (None = all); a cached factorisation is reused when it holds >= k columns.
-        k_compute: how many to compute on a cache miss (None = all, so that any later rank is a slice of this one SVD)."""
-        key, wc = SVDLinear._cache_key(linear, act_aware, alpha)
+        k_compute: how many to compute on a cache miss (None = all, so that any later rank is a slice of this one SVD).
+        ortho: re-orthonormalise the long side's vectors (None: ASVD_SVD_ORTHO).  A refused or unconverged pass is not an error: the factors are
+        then those of the plain call (ASVD_STRICT=1 raises)."""
+        ortho = _ortho(ortho)
+        key, wc = SVDLinear._cache_key(linear, act_aware, alpha, ortho)
         kmax = min(wc.shape)
         k = kmax if k is None else max(1, min(int(k), kmax))
         cache = getattr(linear, "_asvd_factor_cache", None)
@@ -171,32 +180,43 @@ class SVDLinear(nn.Module):
             return cache[1]
         k = kmax if k_compute is None else max(k, min(int(k_compute), kmax))
         s = SVDLinear._scale_vector(linear, act_aware, alpha)
-        U, S, V, info = ops.svd(wc, s, k=k)
+        U, S, V, info = ops.svd(wc, s, k=k, ortho=ortho)
         if info.status == 2:
             raise FloatingPointError("nan in svd")
+        sweeps = 0
         if info.status == 1:
+            sweeps = 60
             # ASVD_N_NOCONV: the sweeps stopped at max_sweeps.  Never cache an unconverged factorisation silently: one retry with a
             # generous sweep budget, then strict mode raises and the default path warns (results of the retry are still returned).
-            U, S, V, info = ops.svd(wc, s, k=k, max_sweeps=60)
+            U, S, V, info = ops.svd(wc, s, k=k, max_sweeps=60, ortho=ortho)
             if info.status == 2:
                 raise FloatingPointError("nan in svd")
             if info.status == 1:
                 if _strict():
                     raise ArithmeticError(f"block-Jacobi SVD of {tuple(wc.shape)} did not converge in 60 sweeps")
                 print(f"warning: SVD of {linear} not converged after 60 sweeps (last rotated pairs {info.last_rotated_pairs})")
+        if info.reorth is not None and info.reorth.status != 0:
+            if _strict():
+                raise ArithmeticError(f"re-orthonormalisation of the singular vectors of {tuple(wc.shape)} refused or not converged: {info.reorth}")
+            print(f"warning: singular vectors of {linear} not re-orthonormalised ({info.reorth}); keeping the plain factors")
+            if info.reorth.passes > 0:  # a pass that ran changed the vectors: the plain call's come from the plain call
+                reorth = info.reorth
+                U, S, V, info = ops.svd(wc, s, k=k, max_sweeps=sweeps)
+                info.reorth = reorth
         linear._asvd_factor_cache = (key, (U, S, V, s))
         linear._asvd_svd_info = info
         return U, S, V, s
 
     @staticmethod
-    def prefactorize(linears, act_aware=False, alpha=1, ranks=None, max_batch=32, concurrent=True):
+    def prefactorize(linears, act_aware=False, alpha=1, ranks=None, max_batch=32, concurrent=True, ortho=None):
         """Factorise many Linears up front, same-shape ones CONCURRENTLY (asvd_svd_batched): independent matrices are what
         fills the 256 CUs during the 64-workgroup eigen-solve phase, and 288 GB of HBM hold the factors of a whole 7B/13B
         shard.  ranks: optional {linear: largest rank needed} (convergence is then only enforced for those leading triplets).
-        Fills the same per-module cache `from_linear` uses; already cached layers are skipped."""
+        Fills the same per-module cache `from_linear` uses; already cached layers are skipped.  ortho: as in factorize."""
+        ortho = _ortho(ortho)
         groups = {}
         for lin in linears:
-            key, wc = SVDLinear._cache_key(lin, act_aware, alpha)
+            key, wc = SVDLinear._cache_key(lin, act_aware, alpha, ortho)
             kmax = min(wc.shape)
             k = kmax if not ranks or not ranks.get(lin) else max(1, min(int(ranks[lin]), kmax))
             cache = getattr(lin, "_asvd_factor_cache", None)
@@ -218,9 +238,9 @@ class SVDLinear(nn.Module):
         def run(chunk):
             k = max(it[4] for it in chunk)
             scs = None if chunk[0][3] is None else [it[3] for it in chunk]
-            U, S, V, infos = ops.svd_batched([it[2] for it in chunk], scs, k=k)
+            U, S, V, infos = ops.svd_batched([it[2] for it in chunk], scs, k=k, ortho=ortho)
             for j, (lin, key, wc, s, _) in enumerate(chunk):
-                if infos[j].status != 0:
+                if infos[j].status != 0 or (infos[j].reorth is not None and infos[j].reorth.status != 0):
                     continue  # NaN / not converged: from_linear -> factorize handles it (retry, strict raise, or NaN fallback)
                 lin._asvd_factor_cache = (key, (U[j], S[j], V[j], s))
                 lin._asvd_svd_info = infos[j]
@@ -313,6 +333,7 @@ class SVDLinear(nn.Module):
         alpha=1,
         sigma_fuse="UV",
         rank_align=1,
+        ortho=None,
     ):
         assert ic_split == 1 or oc_split == 1
         rank = SVDLinear.compute_rank(linear, param_ratio, rank_align)
@@ -325,7 +346,7 @@ class SVDLinear(nn.Module):
             if rank < 1 or rank > min(linear.in_features, linear.out_features):
                 raise ValueError(f"rank {rank} outside [1, min(in, out)]")  # torch.svd_lowrank(q=rank) raises too
             hint = getattr(linear, "_asvd_rank_hint", None)  # set by the sweep: the largest rank it will ask for
-            U, S, V, s = SVDLinear.factorize(linear, act_aware, alpha, k=rank, k_compute=hint)
+            U, S, V, s = SVDLinear.factorize(linear, act_aware, alpha, k=rank, k_compute=hint, ortho=ortho)
         except (AsvdHipError, AttributeError):
             raise
         except Exception:

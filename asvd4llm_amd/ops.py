@@ -153,6 +153,7 @@ class SvdInfo:
 
     def __init__(self, status, sweeps, last_rot, path=0):
         self.status, self.sweeps, self.last_rotated_pairs, self.path = status, sweeps, last_rot, path
+        self.reorth = None  # ReorthInfo of the long side's vectors when the call ran with ortho=True
         self.reduced = bool(path & L.PATH_REDUCED)
         self.reduce_fallback = bool(path & L.PATH_REDUCE_FALLBACK)
         self.plain_retry = bool(path & L.PATH_PLAIN_RETRY)
@@ -165,9 +166,54 @@ class SvdInfo:
                 f"reduce_fallback={self.reduce_fallback}, plain_retry={self.plain_retry}, split={self.split}, gram_retry={self.gram_retry})")
 
 
-def svd_batched(mats, col_scales=None, k=None, want_vectors=True, max_sweeps=0, tol=0.0):
+class ReorthInfo:
+    """per-problem result of asvd_reorth_batched: status (0, N_NOCONV, N_NAN), passes made, max |Q^T Q - I| at entry and measured at exit"""
+
+    def __init__(self, status, passes, e_before, e_after):
+        self.status, self.passes, self.e_before, self.e_after = status, passes, e_before, e_after
+
+    def __repr__(self):
+        return f"ReorthInfo(status={self.status}, passes={self.passes}, e_before={self.e_before:.3g}, e_after={self.e_after:.3g})"
+
+
+def _bits_to_float(i):
+    return ctypes.c_float.from_buffer(ctypes.c_int(i)).value
+
+
+def reorth_batched(Qs, max_passes=0, tol=0.0):
+    """Make the columns of every Q [m, k] (same shape and row stride, fp32, m >= k) orthonormal IN PLACE and in their given order
+    (asvd_reorth_batched: Q <- Q - Q (striu(E) + diag(E) / 2), E = Q^T Q - I, until max |E| <= tol).  Returns [ReorthInfo]; a problem that
+    is refused (entry max |E| > 0.25 or non-finite) is left untouched with a positive status."""
+    lib = L.load(True)
+    B = len(Qs)
+    assert B >= 1
+    m, k = Qs[0].shape
+    dev = Qs[0].device
+    for q in Qs:
+        _dev(q, "Q")
+        assert q.shape == (m, k) and q.dtype == torch.float32 and q.stride(1) == 1 and q.stride(0) == Qs[0].stride(0)
+    ldq = Qs[0].stride(0) if m > 1 else max(Qs[0].stride(0), k)
+    nb = ctypes.c_size_t()
+    L.check(lib.asvd_reorth_worksize(B, m, k, ctypes.byref(nb)), "asvd_reorth_worksize")
+    work = _work(nb.value, dev)
+    arr = ctypes.c_void_p * B
+    info = (ctypes.c_int * (4 * B))()
+    with torch.cuda.device(dev):
+        rc = lib.asvd_reorth_batched(B, arr(*[q.data_ptr() for q in Qs]), m, k, ldq, int(max_passes), float(tol), _ptr(work), work.numel(), info,
+                                     _stream(Qs[0]))
+    L.check(rc, "asvd_reorth_batched")
+    return [ReorthInfo(info[4 * b], info[4 * b + 1], _bits_to_float(info[4 * b + 2]), _bits_to_float(info[4 * b + 3])) for b in range(B)]
+
+
+def reorth(Q, max_passes=0, tol=0.0):
+    return reorth_batched([Q], max_passes, tol)[0]
+
+
+def svd_batched(mats, col_scales=None, k=None, want_vectors=True, max_sweeps=0, tol=0.0, ortho=False):
     """Economy SVD of a list of same-shape device matrices: mats[b] * diag(col_scales[b]) = U S V^T.
-    Returns (U list [m,k], S list [k], V list [n,k], infos).  U/V lists are None when want_vectors is False."""
+    Returns (U list [m,k], S list [k], V list [n,k], infos).  U/V lists are None when want_vectors is False.
+    ortho (with vectors): the long side's vectors (U when m >= n, else V) go through reorth_batched after the factorisation — S and the short
+    side are not touched, infos[b].reorth holds the ReorthInfo (a refused or unconverged pass is reported there, not raised)."""
     lib = L.load(True)
     B = len(mats)
     assert B >= 1
@@ -205,11 +251,15 @@ def svd_batched(mats, col_scales=None, k=None, want_vectors=True, max_sweeps=0, 
         path = int(lib.asvd_svd_get_last_path())
     L.check(rc, "asvd_svd_batched")
     infos = [SvdInfo(info[4 * b], info[4 * b + 1], info[4 * b + 2], path) for b in range(B)]
+    if ortho and want_vectors:
+        del work  # the SVD's workspace (23.9 GiB for 32 x 4096^2) goes back to the allocator before the pass takes its own
+        for i, r in zip(infos, reorth_batched(U if m >= n else V)):
+            i.reorth = r
     return U, S, V, infos
 
 
-def svd(a, col_scale=None, k=None, want_vectors=True, max_sweeps=0, tol=0.0):
-    U, S, V, infos = svd_batched([a], None if col_scale is None else [col_scale], k, want_vectors, max_sweeps, tol)
+def svd(a, col_scale=None, k=None, want_vectors=True, max_sweeps=0, tol=0.0, ortho=False):
+    U, S, V, infos = svd_batched([a], None if col_scale is None else [col_scale], k, want_vectors, max_sweeps, tol, ortho)
     if want_vectors:
         return U[0], S[0], V[0], infos[0]
     return None, S[0], None, infos[0]

@@ -21,6 +21,11 @@ from .modules.svd_linear import SVDLinear
 from .sweep_eval import PrefixCachedEvaluator
 
 
+def _ortho_kw(args):
+    """--svd_ortho (additive flag, read with getattr: callers build `args` by hand): the keyword travels only when it is set"""
+    return {"ortho": True} if getattr(args, "svd_ortho", False) else {}
+
+
 def collect_linear_info(model):
     """{nn.Linear: {"father", "name", "full_name"}} in the order the reference's sweep and search visit the layers (sensitivity.py:19-33,
     binary_search.py:11-27): a module's own Linear children in registration order, then its other children LAST-FIRST, depth first —
@@ -51,7 +56,7 @@ def _multi_rank_module(raw_linear, ratios, args):
     if min(ranks) < 1 or max(ranks) > kmax:
         return None
     try:
-        U, S, V, s = SVDLinear.factorize(raw_linear, True, args.alpha, k=max(ranks), k_compute=getattr(raw_linear, "_asvd_rank_hint", None))
+        U, S, V, s = SVDLinear.factorize(raw_linear, True, args.alpha, k=max(ranks), k_compute=getattr(raw_linear, "_asvd_rank_hint", None), **_ortho_kw(args))
     except Exception:
         return None
     A, B, flags = ops.truncate_split(U, S, V, s, max(ranks), "UV", raw_linear.weight.dtype)  # sweep: from_linear's default sigma_fuse
@@ -104,7 +109,7 @@ def calib_sensitivity_ppl(model, calib_loader, args, use_cache=True):
         l._asvd_rank_hint = max(SVDLinear.compute_rank(l, r, args.rank_align) for r in param_ratio_candidates)
     if keep_cache and getattr(args, "prefactorize", True) and all(l.weight.is_cuda for l in mine):
         SVDLinear.prefactorize(mine, act_aware=True, alpha=args.alpha, ranks={l: l._asvd_rank_hint for l in mine},
-                               max_batch=getattr(args, "svd_batch", 32))
+                               max_batch=getattr(args, "svd_batch", 32), **_ortho_kw(args))
     # prefix-cached evaluation (sweep_eval.py): same perplexities, about half the forward work; --no_fused_sweep disables
     evaluator = None
     if getattr(args, "fused_sweep", True) and n_mine > 0:
@@ -144,6 +149,7 @@ def calib_sensitivity_ppl(model, calib_loader, args, use_cache=True):
                 alpha=args.alpha,
                 act_aware=True,  # hard-coded in the reference sweep (sensitivity.py:50)
                 rank_align=args.rank_align,
+                **_ortho_kw(args),
             )
             setattr(info["father"], info["name"], svd_linear)
             if evaluator is not None:

@@ -201,6 +201,32 @@ int asvd_sigma_max_batched(int batch, const void* const* a_host, int a_dtype, in
                            int* info_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K18  re-orthonormalise columns in their given order (new; the reference gets an orthonormal basis from the QR inside torch.svd_lowrank).
+ * The SVD above returns the short side's vectors orthonormal to 1e-5 but the long side's from one product u_j = A v_j / sigma_j, whose defect
+ * grows with sigma_1 / sigma_j.  This is the opt-in repair, a post-pass on finished output; nothing above calls it.
+ * One pass:  E = Q^T Q - I,  T = striu(E) + diag(E) / 2,  Q <- Q - Q T  (first-order inverse of the Cholesky factor of Q^T Q: every pass multiplies
+ * Q from the right by an upper-triangular matrix with positive diagonal, so span(q_1..q_j) is kept for every j and the limit is the Cholesky-QR
+ * factor of the input).  Passes repeat until max |E| <= tol; the final max |E| is measured by a last Gram pass (p passes cost p + 1 Gram passes).
+ * E is the exact Gram matrix of the columns rounded to 24-bit fixed point (int8 digit products, fp64 combination, identity subtracted before the
+ * rounding to fp32; for m > 32768 the row segments of 32768 are added in fp32); the update runs on the fp32 matrix instructions, in place.
+ *   Q_host      host array [batch] of device pointers to Q_b [m, k] fp32 row-major, leading dim ldq >= k, m >= k >= 1 (any k, any ldq; 4-byte
+ *               aligned); columns [k, ldq) are neither read nor written
+ *   max_passes  <=0: default (8);   tol  <=0: default (2e-6)
+ *   info_host   optional host int[4*batch]: {status, passes, float bits of max |E| at entry, float bits of max |E| measured at exit}
+ * Per problem: entry max |E| non-finite -> ASVD_N_NAN, Q_b untouched; entry max |E| > 0.25 (the iteration is not monotone and diverges from about
+ * 1; a zero column gives E_jj = -1) -> ASVD_N_NOCONV, Q_b untouched; a value >= 1 or non-finite inside the loop, or max_passes reached with
+ * max |E| > tol -> ASVD_N_NOCONV.  One problem's refusal does not touch the others: every problem's arithmetic is its own, so its bits equal
+ * those of a call without the refused one.  Two calls on equal input give equal bits.
+ * Host-synchronous: one stream synchronisation per Gram pass.  The batch runs in sub-batches that keep the workspace at or under 1 GiB (one
+ * problem at a time when one alone needs more): 32 x 4096 x 4096 runs 9 problems at a time in 1008 MiB (per problem: 48 MiB digit planes + 64 MiB T);
+ * 32 x 4096 x 1843 runs 28 at a time in 1003 MiB (35.8 MiB per problem).
+ * Returns worst status over the batch; bad arguments (NULL, batch < 1, k < 1, m < k, ldq < k, misaligned Q) return ASVD_E_BADARG before any device
+ * call, a short workspace ASVD_E_WORKSPACE. */
+int asvd_reorth_worksize(int batch, int64_t m, int64_t k, size_t* bytes);
+int asvd_reorth_batched(int batch, float* const* Q_host, int64_t m, int64_t k, int64_t ldq, int max_passes, float tol, void* work,
+                        size_t work_bytes, int* info_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K5/K6  truncate to rank r, un-scale V, fuse sigma, transpose V, down-cast, NaN flag.
  * Replaces svd_linear.py:69-70 (`V = V / s.view(-1,1)`), :81-98 (NaN checks) and SVDLinear.__init__
  * :16-24 + the `.to(dtype)` at :102:
