@@ -3,7 +3,8 @@ load model -> calibration data -> calib_input_distribution -> sensitivity sweep 
 
 Additive flags only: --calib_dataset synthetic (no network in this image), --random_init <hf config name|json> to build a
 shape-faithful randomly initialised model when no checkpoint is on disk, --exclude_lm_head, --dist (torchrun: one rank per
-GPU, layers sharded, RCCL all-gather of sensitivities)."""
+GPU, layers sharded, RCCL all-gather of sensitivities), --model_dtype float16|bfloat16 (the dtype the model is loaded in; float16 is the
+reference's)."""
 import argparse
 import os
 
@@ -11,17 +12,21 @@ import numpy as np
 import torch
 
 
+MODEL_DTYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16}
+
+
 def build_model(args):
     from transformers import AutoConfig, AutoModelForCausalLM, AutoTokenizer
     tokenizer = None
+    dtype = MODEL_DTYPES[getattr(args, "model_dtype", "float16")]
     if args.random_init:
         from asvd4llm_amd.model_zoo import random_init_model
         # synthetic weights are created on the GPU (seconds instead of ~2 minutes for a 7B-shaped model); ASVD_INIT_ON_CPU=1 keeps the host stream
         init_dev = None if os.environ.get("ASVD_INIT_ON_CPU") == "1" or not torch.cuda.is_available() else "cuda"
-        model = random_init_model(args.model_id, dtype=torch.float16, device=init_dev)
+        model = random_init_model(args.model_id, dtype=dtype, device=init_dev)
     else:
         tokenizer = AutoTokenizer.from_pretrained(args.model_id, trust_remote_code=True)
-        model = AutoModelForCausalLM.from_pretrained(args.model_id, torch_dtype=torch.float16, trust_remote_code=True)
+        model = AutoModelForCausalLM.from_pretrained(args.model_id, torch_dtype=dtype, trust_remote_code=True)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = model.to(dev)
     return model, tokenizer
@@ -176,6 +181,9 @@ def build_parser():
     parser.add_argument("--use_bos", action="store_true", help="use bos token in calibration")
     # ---- additive, build-only flags ----
     parser.add_argument("--random_init", action="store_true", help="shape-faithful random-init model named by --model_id (no checkpoints offline)")
+    parser.add_argument("--model_dtype", type=str, default="float16", choices=sorted(MODEL_DTYPES),
+                        help="dtype the model is loaded in (float16: the reference's behaviour).  A bfloat16 model packs (--weight_quant_storage) into "
+                             "modules with weight_dtype bfloat16, whose bf16 inputs take the packed kernels once ASVD_PACKED_BF16=1 switches them on")
     parser.add_argument("--svd_ortho", action="store_true",
                         help="re-orthonormalise the long side's singular vectors after every factorisation (K18: U = W V / sigma loses orthogonality on "
                              "graded spectra, 2e-3 .. 2.5e-2 measured); matters under --sigma_fuse U / V, where one emitted factor is the raw vector "

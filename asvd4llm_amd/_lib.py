@@ -71,7 +71,12 @@ SIGNATURES = {
     "asvd_lowrank_packed_f16": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_packed_gemm_max_tokens": (_i64, []),
     "asvd_packed_gemm_f16": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
-    "asvd_fro_worksize": (_i, [_i64, _i64, _c.POINTER(_sz)]),
+    "asvd_w8_linear_a16": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_wb_linear_a16": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_packed_gemm_a16": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "asvd_lowrank_packed_a16": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz,
+                                     _vp]),
+    "asvd_fro_worksize":(_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),
     "asvd_reconstruct_err": (_i, [_vp, _i, _i64, _vp, _vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),

@@ -1,6 +1,7 @@
 // w8_linear.hip — K12: forward and dequantization of RTN-quantized weights kept as uint8 codes (W8A16).
 //
 //   asvd_w8_linear_f16   y[T, N] = fp16( x[T, K] . w^T + bias ),   w[n, k] = fp16( scale[n] * (float(q[n, k]) - zero[n]) )
+//   asvd_w8_linear_a16   the same with the activation dtype (fp16 / bf16: K19 below) and the group size as arguments; the _f16 entries forward to it
 //   asvd_w8_dequant      out[n, k] = dtype( scale[n] * (float(q[n, k]) - zero[n]) )
 //
 // w is the value the fake quantizer of rtn_quant.hip writes: the subtraction (exact in fp32), ONE fp32 product, ONE rounding (RNE) to the
@@ -31,6 +32,12 @@
 //
 // K17, inputs beyond decode (asvd_packed_gemm_f16): the same weight and the same operands on a token-tiled GEMM that stages x through LDS once per
 // workgroup and dequantizes a lane's codes once per up to 128 tokens; its description stands with packed_gemm_kernel below.
+//
+// K19, bf16 activations (the asvd_*_a16 entries with act_dtype ASVD_BF16): every forward kernel here takes the activation type ADT as its first
+// template parameter.  The bf16 form has w = bf16(scale * (code - zero)) (the same fp32 value behind the same barrier, ONE packed RNE conversion:
+// the bits w8_dequant_kernel<ASVD_BF16> writes for finite values), v_mfma_f32_32x32x16_bf16 on the same operands (the operand and accumulator
+// layout of the fp16 instruction), a bf16 bias and an RNE-rounded bf16 output (K16: a bf16 z, and a bf16 NaN as poison); everything else is
+// the one text, and the fp16 instantiations are what they were before the parameter existed.
 //
 // Non-finite activations: nothing multiplies a padding zero by an activation that exists (beyond K both operands are zero), so a token row
 // with a NaN / +Inf / -Inf has the class of the fp64 evaluation of the same sums element for element, and every other row keeps its bits.
@@ -73,9 +80,32 @@ __device__ __forceinline__ float w8_value(uint32_t code, float scale, float zero
 
 typedef float w8_f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 w8_f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 w8_bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 w8_bf16x8 __attribute__((ext_vector_type(8)));
+
+// ADT, the activation type of the forward kernels (ASVD_F16 or ASVD_BF16): the type of x, bias, y and of the weight operand the codes are
+// dequantized to.  The two forms differ in the four helpers below (pair conversion, element load, element store, matrix instruction) and in
+// the NaN K16 poisons with; tiles, k permutation, split of k over the waves and the order of every sum are one text.
+// two fp32 values -> one packed pair, ONE rounding (RNE) each (bf16: v_cvt_pk_bf16_f32).  For finite values the bf16 bits are those of
+// f32_to_bf16_bits (common.h), which is what w8_dequant_kernel<ASVD_BF16> writes
+template <int ADT>
+__device__ __forceinline__ uint32_t w8_cvt_pair(w8_f32x2 v) {
+    if constexpr (ADT == ASVD_BF16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, w8_bf16x2));
+    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, w8_f16x2));
+}
+template <int ADT>
+__device__ __forceinline__ float w8_act_to_f32(uint16_t b) {
+    return ADT == ASVD_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b);
+}
+template <int ADT>
+__device__ __forceinline__ uint16_t w8_f32_to_act(float v) {
+    if constexpr (ADT == ASVD_BF16) return __builtin_bit_cast(uint16_t, (__bf16)v);   // RNE
+    else return f32_to_f16_bits(v);
+}
+template <int ADT> constexpr uint16_t W8_ACT_NAN = ADT == ASVD_BF16 ? 0x7fc0 : 0x7e00;   // 0x7e00 is a FINITE bf16 number
 
 // 16 codes -> the two 8-value MFMA operands (one packed conversion per pair of codes); elements at or beyond `valid` are zero
-template <int BITS, bool MASK>
+template <int ADT, int BITS, bool MASK>
 __device__ __forceinline__ void w8_chunk_f16(const uint32_t (&w)[W8_CW<BITS>], float scale, float zero, int valid, uint4& w0, uint4& w1) {
     uint32_t h[8];
 #pragma unroll
@@ -83,8 +113,8 @@ __device__ __forceinline__ void w8_chunk_f16(const uint32_t (&w)[W8_CW<BITS>], f
         w8_f32x2 a, b;
         a.x = w8_value(w8_code<BITS>(w, 2 * p), scale, zero), a.y = w8_value(w8_code<BITS>(w, 2 * p + 1), scale, zero);
         b.x = w8_value(w8_code<BITS>(w, 2 * p + 2), scale, zero), b.y = w8_value(w8_code<BITS>(w, 2 * p + 3), scale, zero);
-        h[p] = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, w8_f16x2));
-        h[p + 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(b, w8_f16x2));
+        h[p] = w8_cvt_pair<ADT>(a);
+        h[p + 1] = w8_cvt_pair<ADT>(b);
         if (MASK) {
             h[p] &= (valid > 2 * p ? 0xffffu : 0u) | (valid > 2 * p + 1 ? 0xffff0000u : 0u);
             h[p + 1] &= (valid > 2 * p + 2 ? 0xffffu : 0u) | (valid > 2 * p + 3 ? 0xffff0000u : 0u);
@@ -113,7 +143,7 @@ __device__ __forceinline__ uint4 w8_load_codes_tail(const uint8_t* __restrict__ 
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// 8 fp16 values at p[0..7], the first `valid` of them readable
+// 8 fp16 / bf16 values at p[0..7], the first `valid` of them readable
 __device__ __forceinline__ uint4 w8_load_x_tail(const uint16_t* __restrict__ p, int valid) {
     uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -122,8 +152,12 @@ __device__ __forceinline__ uint4 w8_load_x_tail(const uint16_t* __restrict__ p, 
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+template <int ADT>
 __device__ __forceinline__ f32x16 w8_mfma(const uint4& a, const uint4& b, f32x16 acc) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+    if constexpr (ADT == ASVD_BF16)
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(w8_bf16x8, a), __builtin_bit_cast(w8_bf16x8, b), acc, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
 }
 
 // one iteration of a lane: its 64 codes (8 BITS bytes) and 64 x values (16-byte loads), and the 8 MFMAs that consume them
@@ -141,27 +175,27 @@ __device__ __forceinline__ void w8_iter_load(uint4 (&cv)[W8_CW<BITS>], uint4 (&x
     }
 }
 
-template <int BITS>
+template <int ADT, int BITS>
 __device__ __forceinline__ f32x16 w8_iter_mfma(const uint4 (&cv)[W8_CW<BITS>], const uint4 (&xv)[8], float sc, float zr, f32x16 acc) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         uint32_t w[W8_CW<BITS>];
         uint4 w0, w1;
         w8_chunk_words<BITS>(cv, m, w);
-        w8_chunk_f16<BITS, false>(w, sc, zr, 16, w0, w1);
-        acc = w8_mfma(xv[2 * m], w0, acc);
-        acc = w8_mfma(xv[2 * m + 1], w1, acc);
+        w8_chunk_f16<ADT, BITS, false>(w, sc, zr, 16, w0, w1);
+        acc = w8_mfma<ADT>(xv[2 * m], w0, acc);
+        acc = w8_mfma<ADT>(xv[2 * m + 1], w1, acc);
     }
     return acc;
 }
 
-// One (32-token, ft-feature) tile of y = fp16(x w^T + bias), tokens t0.., features n0.., by the whole workgroup: the tile loop, the LDS
+// One (32-token, ft-feature) tile of y = ADT(x w^T + bias), tokens t0.., features n0.., by the whole workgroup: the tile loop, the LDS
 // reduction in its fixed order, bias and store.  w8_linear_kernel is one call of it; the packed pair calls it once per unit of a phase (the
 // caller separates two calls by a __syncthreads(): red is reused).
 // BITS = 8: q holds one code per byte, ldq >= K.  BITS = 6, 4: q holds the bitstream rows (ldq bytes apart), K % 16 == 0 and everything is
 // 16-byte aligned (vec is 1).  GROUPED: scale / zero are [N, ng], a group is 1 << gshift codes; K % 16 == 0 and vec is 1 at every width.
 // XCOH: x is the pair's intermediate (z_load16; vec is 1 and K % 16 == 0, no element loads of x).  ZOUT: y is that intermediate (z_store).
-template <int BITS, bool GROUPED, bool XCOH, bool ZOUT>
+template <int ADT, int BITS, bool GROUPED, bool XCOH, bool ZOUT>
 __device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
                                         const float* __restrict__ scale, const float* __restrict__ zero, const uint16_t* __restrict__ bias, int N,
                                         int K, uint16_t* __restrict__ y, int t0, int n0, int ft,
@@ -197,7 +231,7 @@ __device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const u
             }
         }
 #pragma unroll
-        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma<BITS>(cv[u], xv[u], GROUPED ? gs[u] : sc, GROUPED ? gz[u] : zr, acc);
+        for (int u = 0; u < W8_U; ++u) acc = w8_iter_mfma<ADT, BITS>(cv[u], xv[u], GROUPED ? gs[u] : sc, GROUPED ? gz[u] : zr, acc);
     }
     for (; base < nkfull; base += W8_WAVES) {
         uint4 cv[W8_CW<BITS>], xv[8];
@@ -206,7 +240,7 @@ __device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const u
             const int gi = (base * W8_KIT + 64 * g) >> gshift;
             sc = srow[gi], zr = zrow[gi];
         }
-        acc = w8_iter_mfma<BITS>(cv, xv, sc, zr, acc);
+        acc = w8_iter_mfma<ADT, BITS>(cv, xv, sc, zr, acc);
     }
 
     // ---- what is left (K % 128, or every iteration when the rows are not 16-byte aligned): chunk by chunk, zero beyond K ----
@@ -261,9 +295,9 @@ __device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const u
                 for (int t = 0; t < W8_CW<BITS>; ++t) w[t] = w8_word(c, t & 3);
             }
             uint4 w0, w1;
-            w8_chunk_f16<BITS, true>(w, sc, zr, valid, w0, w1);
-            acc = w8_mfma(x0, w0, acc);
-            acc = w8_mfma(x1, w1, acc);
+            w8_chunk_f16<ADT, BITS, true>(w, sc, zr, valid, w0, w1);
+            acc = w8_mfma<ADT>(x0, w0, acc);
+            acc = w8_mfma<ADT>(x1, w1, acc);
         }
     }
 
@@ -277,20 +311,20 @@ __device__ __forceinline__ void w8_tile(float (&red)[W8_WAVES][16 * 64], const u
         const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5), col = l & 31;   // token, feature of accumulator register `reg` of lane `l`
         if (col < nvalid && row < tvalid) {
             float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-            if (bias) v += f16_bits_to_f32(bias[n0 + col]);
-            if constexpr (ZOUT) z_store(y + (int64_t)(t0 + row) * N + n0 + col, f32_to_f16_bits(v));
-            else y[(int64_t)(t0 + row) * N + n0 + col] = f32_to_f16_bits(v);
+            if (bias) v += w8_act_to_f32<ADT>(bias[n0 + col]);
+            if constexpr (ZOUT) z_store(y + (int64_t)(t0 + row) * N + n0 + col, w8_f32_to_act<ADT>(v));
+            else y[(int64_t)(t0 + row) * N + n0 + col] = w8_f32_to_act<ADT>(v);
         }
     }
 }
 
-template <int BITS, bool GROUPED>
+template <int ADT, int BITS, bool GROUPED>
 __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
                                                               const float* __restrict__ scale, const float* __restrict__ zero,
                                                               const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ft,
                                                               int nkfull, int vec, int ng, int gshift) {
     __shared__ float red[W8_WAVES][16 * 64];
-    w8_tile<BITS, GROUPED, false, false>(red, x, T, q, ldq, scale, zero, bias, N, K, y, blockIdx.y * 32, blockIdx.x * ft, ft, nkfull, vec, ng, gshift);
+    w8_tile<ADT, BITS, GROUPED, false, false>(red, x, T, q, ldq, scale, zero, bias, N, K, y, blockIdx.y * 32, blockIdx.x * ft, ft, nkfull, vec, ng, gshift);
 }
 
 // ---- K16: a packed SVDLinear factor pair in one launch --------------------------------------------------------------------------------
@@ -302,7 +336,7 @@ __global__ __launch_bounds__(W8_THREADS) void w8_linear_kernel(const uint16_t* _
 // bits of the two launches it replaces.  z ([round_up(T, 32), r] fp16 behind the 256-byte barrier block of the workspace) is stored and loaded
 // at agent scope; rows at or beyond T and nothing else of it stay unwritten and are never read (token rows are clamped as in the tile loop).
 // A workgroup takes units blockIdx.x, + gridDim.x, ...; one without a unit in a phase still arrives at the barrier.
-template <int BITS, bool GROUPED>
+template <int ADT, int BITS, bool GROUPED>
 __global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ qB,
                                                                       int64_t ldB, const float* __restrict__ scaleB, const float* __restrict__ zeroB,
                                                                       const uint8_t* __restrict__ qA, int64_t ldA, const float* __restrict__ scaleA,
@@ -315,7 +349,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uin
     const int ngB = GROUPED ? (K + (1 << gshift) - 1) >> gshift : 1, ngA = GROUPED ? (r + (1 << gshift) - 1) >> gshift : 1;
 
     for (int u = blockIdx.x; u < nT * ns1; u += G) {
-        w8_tile<BITS, GROUPED, false, true>(red, x, T, qB, ldB, scaleB, zeroB, nullptr, r, K, z, (u / ns1) * 32, (u % ns1) * ft1, ft1, K / W8_KIT, 1,
+        w8_tile<ADT, BITS, GROUPED, false, true>(red, x, T, qB, ldB, scaleB, zeroB, nullptr, r, K, z, (u / ns1) * 32, (u % ns1) * ft1, ft1, K / W8_KIT, 1,
                                             ngB, gshift);
         __syncthreads();
     }
@@ -323,7 +357,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uin
     grid_barrier(bar, (unsigned)G);
 
     for (int u = blockIdx.x; u < nT * ns2; u += G) {
-        w8_tile<BITS, GROUPED, true, false>(red, z, T, qA, ldA, scaleA, zeroA, bias, N, r, y, (u / ns2) * 32, (u % ns2) * ft2, ft2, r / W8_KIT, 1,
+        w8_tile<ADT, BITS, GROUPED, true, false>(red, z, T, qA, ldA, scaleA, zeroA, bias, N, r, y, (u / ns2) * 32, (u % ns2) * ft2, ft2, r / W8_KIT, 1,
                                             ngA, gshift);
         __syncthreads();
     }
@@ -332,7 +366,7 @@ __global__ __launch_bounds__(W8_THREADS, 1) void lowrank_packed_kernel(const uin
             const int t0 = (u / ns2) * 32, n0 = (u % ns2) * ft2, nvalid = min(ft2, N - n0);
             for (int e = threadIdx.x; e < 1024; e += W8_THREADS) {
                 const int row = e >> 5, col = e & 31;
-                if (col < nvalid && t0 + row < T) y[(int64_t)(t0 + row) * N + n0 + col] = 0x7e00;  // fp16 NaN
+                if (col < nvalid && t0 + row < T) y[(int64_t)(t0 + row) * N + n0 + col] = W8_ACT_NAN<ADT>;
             }
         }
 }
@@ -380,7 +414,7 @@ __device__ __forceinline__ void pg_load_codes(uint4 (&cv)[W8_CW<BITS>], float& s
 
 // one step of a wave: dequantize the lane's block, and for each of the MS token sub-tiles the 8 MFMAs on the x operands of LDS rows
 // row0 + 32 s + i (row0 = kg BM).  MASK: the step crosses K, chunks at or beyond K are zero
-template <int BITS, int MS, bool MASK>
+template <int ADT, int BITS, int MS, bool MASK>
 __device__ __forceinline__ void pg_step(f32x16 (&acc)[MS], const uint4 (&cv)[W8_CW<BITS>], float sc, float zr, const uint4* __restrict__ tile, int row0,
                                         int i, int g, int kleft /* K - first k of the lane's block */) {
 #pragma unroll
@@ -388,18 +422,18 @@ __device__ __forceinline__ void pg_step(f32x16 (&acc)[MS], const uint4 (&cv)[W8_
         uint32_t w[W8_CW<BITS>];
         uint4 w0, w1;
         w8_chunk_words<BITS>(cv, m, w);
-        w8_chunk_f16<BITS, MASK>(w, sc, zr, MASK ? max(0, min(16, kleft - 16 * m)) : 16, w0, w1);
+        w8_chunk_f16<ADT, BITS, MASK>(w, sc, zr, MASK ? max(0, min(16, kleft - 16 * m)) : 16, w0, w1);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int s = 0; s < MS; ++s) {
                 const uint4 xa = tile[(row0 + 32 * s + i) * 16 + ((8 * g + 2 * m + h) ^ (i & 15))];
-                acc[s] = w8_mfma(xa, h ? w1 : w0, acc[s]);
+                acc[s] = w8_mfma<ADT>(xa, h ? w1 : w0, acc[s]);
             }
     }
 }
 
-template <int BITS, bool GROUPED, int MS>
+template <int ADT, int BITS, bool GROUPED, int MS>
 __global__ __launch_bounds__(W8_THREADS, 2) void packed_gemm_kernel(const uint16_t* __restrict__ x, int T, const uint8_t* __restrict__ q, int64_t ldq,
                                                                    const float* __restrict__ scale, const float* __restrict__ zero,
                                                                    const uint16_t* __restrict__ bias, int N, int K, uint16_t* __restrict__ y, int ng,
@@ -463,8 +497,8 @@ __global__ __launch_bounds__(W8_THREADS, 2) void packed_gemm_kernel(const uint16
         if (ss + 1 < nss) stage_load(ss + 1);
         if (itn < nk) pg_load_codes<BITS, GROUPED>(cvn, scn, zrn, qrow, srow, zrow, itn, g, K, ng, gshift, (itn + 1) * W8_KIT <= K);
         const uint4* tile = lds + (ss & 1) * PG_TILE_SLOTS;
-        if ((it + 1) * W8_KIT <= K) pg_step<BITS, MS, false>(acc, cv, sc, zr, tile, kg * BM, i, g, 64);
-        else if (it < nk) pg_step<BITS, MS, true>(acc, cv, sc, zr, tile, kg * BM, i, g, K - it * W8_KIT - 64 * g);
+        if ((it + 1) * W8_KIT <= K) pg_step<ADT, BITS, MS, false>(acc, cv, sc, zr, tile, kg * BM, i, g, 64);
+        else if (it < nk) pg_step<ADT, BITS, MS, true>(acc, cv, sc, zr, tile, kg * BM, i, g, K - it * W8_KIT - 64 * g);
         if (ss + 1 < nss) stage_write((ss + 1) & 1);   // the buffer of super-step ss - 1: every wave has passed the barrier that ended it
 #pragma unroll
         for (int m = 0; m < W8_CW<BITS>; ++m) cv[m] = cvn[m];
@@ -491,7 +525,7 @@ __global__ __launch_bounds__(W8_THREADS, 2) void packed_gemm_kernel(const uint16
         }
     }
     if (kg == 0 && n0 + i < N) {   // accumulator register r of lane (i, g): token (r & 3) + 8 (r >> 2) + 4 g of the sub-tile, feature i
-        const float b = bias ? f16_bits_to_f32(bias[n0 + i]) : 0.f;
+        const float b = bias ? w8_act_to_f32<ADT>(bias[n0 + i]) : 0.f;
 #pragma unroll
         for (int s = 0; s < MS; ++s)
 #pragma unroll
@@ -500,7 +534,7 @@ __global__ __launch_bounds__(W8_THREADS, 2) void packed_gemm_kernel(const uint16
                 if (tok < T) {
                     float v = acc[s][r];
                     if (bias) v += b;
-                    y[(int64_t)tok * N + n0 + i] = f32_to_f16_bits(v);
+                    y[(int64_t)tok * N + n0 + i] = w8_f32_to_act<ADT>(v);
                 }
             }
     }
@@ -649,12 +683,16 @@ int w8_feature_tile(int nT, int64_t N, int cus) {
     return ft;
 }
 
+// the activation types of the forward kernels
+inline bool w8_act_ok(int adt) { return adt == ASVD_F16 || adt == ASVD_BF16; }
+
 // group: 0 (scale / zero [N]) or 64 / 128 (K14: [N, ceil(K / group)]); the entry points have checked it
-int w8_linear_launch(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int group, const void* bias,
+template <int ADT>
+int w8_linear_go(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int group, const void* bias,
                      int64_t N, int64_t K, void* y, void* stream) {
     if (!x || !q || !scale || !zero || !y) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || ldq < K || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // 2-byte elements
     if (group && (K % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16 || ldq % 16)) return ASVD_E_BADARG;   // grouped: 16-byte loads only
     int cus = 0;
     const int st = w8_cu_count(&cus);
@@ -664,15 +702,22 @@ int w8_linear_launch(const void* x, int64_t T, const void* q, int64_t ldq, const
     const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)q % 16 == 0) && (K % 8 == 0) && (ldq % 16 == 0);
     const int nkfull = vec ? (int)(K / W8_KIT) : 0;
     if (group)
-        hipLaunchKernelGGL((w8_linear_kernel<8, true>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 8, true>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
                            (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
                            nkfull, 1, (int)ceil_div64(K, group), group == 64 ? 6 : 7);
     else
-        hipLaunchKernelGGL((w8_linear_kernel<8, false>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 8, false>), dim3((unsigned)ceil_div64(N, ft), (unsigned)nT), dim3(W8_THREADS), 0, (hipStream_t)stream,
                            (const uint16_t*)x, (int)T, (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft,
                            nkfull, vec ? 1 : 0, 1, 0);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
+}
+
+int w8_linear_launch(const void* x, int adt, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int group, const void* bias,
+                     int64_t N, int64_t K, void* y, void* stream) {
+    if (!w8_act_ok(adt)) return ASVD_E_BADARG;
+    return adt == ASVD_BF16 ? w8_linear_go<ASVD_BF16>(x, T, q, ldq, scale, zero, group, bias, N, K, y, stream)
+                            : w8_linear_go<ASVD_F16>(x, T, q, ldq, scale, zero, group, bias, N, K, y, stream);
 }
 
 int w8_dequant_launch(const void* q, int64_t ldq, const float* scale, const float* zero, int group, int64_t rows, int64_t cols, void* out,
@@ -722,12 +767,13 @@ int wb_dequant_launch(const void* q, int64_t ld_bytes, int bits, const float* sc
     return ASVD_OK;
 }
 
-int wb_linear_launch(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int group,
+template <int ADT>
+int wb_linear_go(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int group,
                      const void* bias, int64_t N, int64_t K, void* y, void* stream) {
     if (!x || !q || !scale || !zero || !y || (bits != 4 && bits != 6)) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_W8_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256) return ASVD_E_BADARG;
     if (ld_bytes < wb_row_bytes(K, bits) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
-    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // 2-byte elements
     int cus = 0;
     const int st = w8_cu_count(&cus);
     if (st != ASVD_OK) return st;
@@ -736,26 +782,33 @@ int wb_linear_launch(const void* x, int64_t T, const void* q, int64_t ld_bytes, 
     const dim3 grid((unsigned)ceil_div64(N, ft), (unsigned)nT);
     const int ng = group ? (int)ceil_div64(K, group) : 1, gshift = group == 64 ? 6 : 7;
     if (group && bits == 6)
-        hipLaunchKernelGGL((w8_linear_kernel<6, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 6, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
                            ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, ng, gshift);
     else if (group)
-        hipLaunchKernelGGL((w8_linear_kernel<4, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 4, true>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
                            ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, ng, gshift);
     else if (bits == 6)
-        hipLaunchKernelGGL((w8_linear_kernel<6, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 6, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
                            ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, 1, 0);
     else
-        hipLaunchKernelGGL((w8_linear_kernel<4, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
+        hipLaunchKernelGGL((w8_linear_kernel<ADT, 4, false>), grid, dim3(W8_THREADS), 0, (hipStream_t)stream, (const uint16_t*)x, (int)T, (const uint8_t*)q,
                            ld_bytes, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ft, (int)(K / W8_KIT), 1, 1, 0);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
 }
 
-template <int BITS, bool GROUPED>
+int wb_linear_launch(const void* x, int adt, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int group,
+                     const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (!w8_act_ok(adt)) return ASVD_E_BADARG;
+    return adt == ASVD_BF16 ? wb_linear_go<ASVD_BF16>(x, T, q, ld_bytes, bits, scale, zero, group, bias, N, K, y, stream)
+                            : wb_linear_go<ASVD_F16>(x, T, q, ld_bytes, bits, scale, zero, group, bias, N, K, y, stream);
+}
+
+template <int ADT, int BITS, bool GROUPED>
 void lowrank_packed_go(int grid, hipStream_t stream, const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB,
                        const void* qA, int64_t ldA, const float* scaleA, const float* zeroA, const void* bias, int64_t N, int64_t K, int64_t r, void* y,
                        void* work, int ft1, int ft2, int gshift) {
-    hipLaunchKernelGGL((lowrank_packed_kernel<BITS, GROUPED>), dim3((unsigned)grid), dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T,
+    hipLaunchKernelGGL((lowrank_packed_kernel<ADT, BITS, GROUPED>), dim3((unsigned)grid), dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T,
                        (const uint8_t*)qB, ldB, scaleB, zeroB, (const uint8_t*)qA, ldA, scaleA, zeroA, (const uint16_t*)bias, (int)N, (int)K, (int)r,
                        (uint16_t*)y, (uint16_t*)((char*)work + 256), (unsigned*)work, ft1, ft2, gshift);
 }
@@ -768,11 +821,11 @@ int pg_sub_tiles(int64_t T, int64_t N, int cus) {
     return 1;
 }
 
-template <int BITS, bool GROUPED>
+template <int ADT, int BITS, bool GROUPED>
 void pg_go(int ms, hipStream_t stream, const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias,
            int64_t N, int64_t K, void* y, int ng, int gshift) {
     const dim3 grid((unsigned)ceil_div64(N, 32 * ms), (unsigned)ceil_div64(T, 32 * ms));
-#define ASVD_PG_LAUNCH(MS) hipLaunchKernelGGL((packed_gemm_kernel<BITS, GROUPED, MS>), grid, dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T, \
+#define ASVD_PG_LAUNCH(MS) hipLaunchKernelGGL((packed_gemm_kernel<ADT, BITS, GROUPED, MS>), grid, dim3(W8_THREADS), 0, stream, (const uint16_t*)x, (int)T, \
                                               (const uint8_t*)q, ldq, scale, zero, (const uint16_t*)bias, (int)N, (int)K, (uint16_t*)y, ng, gshift)
     if (ms == 4) ASVD_PG_LAUNCH(4);
     else if (ms == 2) ASVD_PG_LAUNCH(2);
@@ -785,19 +838,20 @@ void pg_go(int ms, hipStream_t stream, const void* x, int64_t T, const void* q, 
 extern "C" {
 
 size_t asvd_lowrank_packed_work_bytes(int64_t T, int64_t r) {
-    // [barrier: 256 bytes][z: 32 * ceil(T / 32) x r fp16]
+    // [barrier: 256 bytes][z: 32 * ceil(T / 32) x r fp16 or bf16]
     return 256 + (size_t)(round_up64(T, 32) * r) * sizeof(uint16_t);
 }
 
-int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB, const void* qA,
-                            int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias, int64_t N, int64_t K,
-                            int64_t r, void* y, void* work, size_t work_bytes, void* stream) {
+int asvd_lowrank_packed_a16(const void* x, int act_dtype, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB,
+                            const void* qA, int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias, int64_t N,
+                            int64_t K, int64_t r, void* y, void* work, size_t work_bytes, void* stream) {
+    if (!w8_act_ok(act_dtype)) return ASVD_E_BADARG;
     if (!x || !qB || !scaleB || !zeroB || !qA || !scaleA || !zeroA || !y || !work) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_W8_MAX_TOKENS || (bits != 8 && bits != 6 && bits != 4) || (group != 0 && group != 64 && group != 128)) return ASVD_E_BADARG;
     if (N < 1 || K < 1 || r < 1 || K % 16 || r % 16 || N > 0x7fffffff - 64 || K > 0x7fffffff - 256 || r > 0x7fffffff - 256) return ASVD_E_BADARG;
     if (((uintptr_t)x | (uintptr_t)qB | (uintptr_t)qA | (uintptr_t)work) % 16 || ldB % 16 || ldA % 16) return ASVD_E_BADARG;   // 16-byte loads only
     if (ldB < (bits == 8 ? K : wb_row_bytes(K, bits)) || ldA < (bits == 8 ? r : wb_row_bytes(r, bits))) return ASVD_E_BADARG;
-    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // 2-byte elements
     if (work_bytes < asvd_lowrank_packed_work_bytes(T, r)) return ASVD_E_WORKSPACE;
     int cus = 0;
     const int st = w8_cu_count(&cus);
@@ -807,8 +861,15 @@ int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ld
     const int64_t units1 = nT * ceil_div64(r, ft1), units2 = nT * ceil_div64(N, ft2), units = units1 > units2 ? units1 : units2;
     const int grid = (int)(units < cus ? units : cus);   // <= one workgroup per CU: co-resident, the in-kernel barrier cannot deadlock
     const int gshift = group == 64 ? 6 : 7;
-#define ASVD_LRP_GO(B, GR) lowrank_packed_go<B, GR>(grid, (hipStream_t)stream, x, T, qB, ldB, scaleB, zeroB, qA, ldA, scaleA, zeroA, bias, N, K, r, y, \
-                                                   work, ft1, ft2, gshift)
+#define ASVD_LRP_GO(B, GR)                                                                                                                          \
+    do {                                                                                                                                            \
+        if (act_dtype == ASVD_BF16)                                                                                                                 \
+            lowrank_packed_go<ASVD_BF16, B, GR>(grid, (hipStream_t)stream, x, T, qB, ldB, scaleB, zeroB, qA, ldA, scaleA, zeroA, bias, N, K, r, y, work, \
+                                                ft1, ft2, gshift);                                                                                  \
+        else                                                                                                                                        \
+            lowrank_packed_go<ASVD_F16, B, GR>(grid, (hipStream_t)stream, x, T, qB, ldB, scaleB, zeroB, qA, ldA, scaleA, zeroA, bias, N, K, r, y, work, \
+                                               ft1, ft2, gshift);                                                                                   \
+    } while (0)
     if (group) {
         if (bits == 8) ASVD_LRP_GO(8, true);
         else if (bits == 6) ASVD_LRP_GO(6, true);
@@ -823,17 +884,30 @@ int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ld
     return ASVD_OK;
 }
 
+int asvd_lowrank_packed_f16(const void* x, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB, const void* qA,
+                            int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias, int64_t N, int64_t K,
+                            int64_t r, void* y, void* work, size_t work_bytes, void* stream) {
+    return asvd_lowrank_packed_a16(x, ASVD_F16, T, qB, ldB, scaleB, zeroB, qA, ldA, scaleA, zeroA, bits, group, bias, N, K, r, y, work, work_bytes,
+                                   stream);
+}
+
 int64_t asvd_w8_linear_max_tokens(void) { return ASVD_W8_MAX_TOKENS; }
 
 int asvd_w8_linear_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, const void* bias, int64_t N,
                        int64_t K, void* y, void* stream) {
-    return w8_linear_launch(x, T, q, ldq, scale, zero, 0, bias, N, K, y, stream);
+    return w8_linear_launch(x, ASVD_F16, T, q, ldq, scale, zero, 0, bias, N, K, y, stream);
 }
 
 int asvd_w8_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group,
                                const void* bias, int64_t N, int64_t K, void* y, void* stream) {
     if (group != 64 && group != 128) return ASVD_E_BADARG;
-    return w8_linear_launch(x, T, q, ldq, scale, zero, (int)group, bias, N, K, y, stream);
+    return w8_linear_launch(x, ASVD_F16, T, q, ldq, scale, zero, (int)group, bias, N, K, y, stream);
+}
+
+int asvd_w8_linear_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group,
+                       const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (group != 0 && group != 64 && group != 128) return ASVD_E_BADARG;
+    return w8_linear_launch(x, act_dtype, T, q, ldq, scale, zero, (int)group, bias, N, K, y, stream);
 }
 
 int asvd_w8_dequant(const void* q, int64_t ldq, const float* scale, const float* zero, int64_t rows, int64_t cols, void* out, int out_dtype,
@@ -877,30 +951,41 @@ int asvd_wb_dequant_grouped(const void* q, int64_t ld_bytes, int bits, const flo
 
 int asvd_wb_linear_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, const void* bias,
                        int64_t N, int64_t K, void* y, void* stream) {
-    return wb_linear_launch(x, T, q, ld_bytes, bits, scale, zero, 0, bias, N, K, y, stream);
+    return wb_linear_launch(x, ASVD_F16, T, q, ld_bytes, bits, scale, zero, 0, bias, N, K, y, stream);
 }
 
 int asvd_wb_linear_grouped_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
                                int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream) {
     if (group != 64 && group != 128) return ASVD_E_BADARG;
-    return wb_linear_launch(x, T, q, ld_bytes, bits, scale, zero, (int)group, bias, N, K, y, stream);
+    return wb_linear_launch(x, ASVD_F16, T, q, ld_bytes, bits, scale, zero, (int)group, bias, N, K, y, stream);
+}
+
+int asvd_wb_linear_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                       int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (group != 0 && group != 64 && group != 128) return ASVD_E_BADARG;
+    return wb_linear_launch(x, act_dtype, T, q, ld_bytes, bits, scale, zero, (int)group, bias, N, K, y, stream);
 }
 
 int64_t asvd_packed_gemm_max_tokens(void) { return ASVD_PACKED_GEMM_MAX_TOKENS; }
 
-int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group,
-                         const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+int asvd_packed_gemm_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                         int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    if (!w8_act_ok(act_dtype)) return ASVD_E_BADARG;
     if (!x || !q || !scale || !zero || !y) return ASVD_E_BADARG;
     if ((bits != 8 && bits != 6 && bits != 4) || (group != 0 && group != 64 && group != 128)) return ASVD_E_BADARG;
     if (T < 1 || T > ASVD_PACKED_GEMM_MAX_TOKENS || N < 1 || K < 1 || K % 16 || N > 0x7fffffff - 128 || K > 0x7fffffff - 512) return ASVD_E_BADARG;
     if (ld_bytes < (bits == 8 ? K : wb_row_bytes(K, bits)) || ld_bytes % 16 || (uintptr_t)x % 16 || (uintptr_t)q % 16) return ASVD_E_BADARG;   // 16-byte loads only
-    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // fp16 elements
+    if (((uintptr_t)y | (uintptr_t)bias) & 1) return ASVD_E_BADARG;   // 2-byte elements
     int cus = 0;
     const int st = w8_cu_count(&cus);
     if (st != ASVD_OK) return st;
     const int ms = pg_sub_tiles(T, N, cus);
     const int ng = group ? (int)ceil_div64(K, group) : 1, gshift = group == 64 ? 6 : 7;
-#define ASVD_PG_GO(B, GR) pg_go<B, GR>(ms, (hipStream_t)stream, x, T, q, ld_bytes, scale, zero, bias, N, K, y, ng, gshift)
+#define ASVD_PG_GO(B, GR)                                                                                                         \
+    do {                                                                                                                          \
+        if (act_dtype == ASVD_BF16) pg_go<ASVD_BF16, B, GR>(ms, (hipStream_t)stream, x, T, q, ld_bytes, scale, zero, bias, N, K, y, ng, gshift); \
+        else pg_go<ASVD_F16, B, GR>(ms, (hipStream_t)stream, x, T, q, ld_bytes, scale, zero, bias, N, K, y, ng, gshift);              \
+    } while (0)
     if (group) {
         if (bits == 8) ASVD_PG_GO(8, true);
         else if (bits == 6) ASVD_PG_GO(6, true);
@@ -913,6 +998,11 @@ int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_byt
 #undef ASVD_PG_GO
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
+}
+
+int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero, int64_t group,
+                         const void* bias, int64_t N, int64_t K, void* y, void* stream) {
+    return asvd_packed_gemm_a16(x, ASVD_F16, T, q, ld_bytes, bits, scale, zero, group, bias, N, K, y, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,10 @@ import torch.nn.functional as F
 # 0.84, then 1.04 / 1.30.  6-bit rows and group-wise scales (measured on 8 of the 32 blocks) cross between 256 and 512 as well; byte codes with
 # groups of 64 on the plain set are level at 256 (1.007, inside the dense path's spread).  Above the constant the dense path is faster and costs an
 # out x in fp16 temporary per call (90 MB for an 11008 x 4096 layer).
+# bf16 inputs (packed_bf16_enabled) take the same constant.  Measured once for bf16 (tools/bench_w8_forward.py --gemm --dtype bf16, one run on one
+# MI355X, profiles/w8_forward_bf16.json): against dequantize + F.linear in bf16 the kernel takes 0.55 / 0.56 / 0.73 / 0.85 of the time at 32 / 64 /
+# 128 / 256 tokens with byte codes on the plain set and 1.31 / 1.34 at 512 / 2048 (ASVD-0.9 set 0.58 / 0.59 / 0.63 / 0.83, then 1.04 / 1.30; 4-bit
+# rows with G = 128 on 8 blocks 0.54 / 0.56 / 0.77 / 0.88, then 1.47 / 1.52): the fp16 crossover, between 256 and 512.
 PACKED_GEMM_MAX_TOKENS = 256
 
 
@@ -22,6 +26,14 @@ def packed_gemm_enabled():
     """The token-tiled GEMM on the codes is opt-in (ASVD_PACKED_GEMM=1, or `module.packed_gemm = True` on one packed Linear): it avoids the
     out x in fp16 temporary of dequantize + F.linear; off, every input beyond decode size keeps that path."""
     return os.environ.get("ASVD_PACKED_GEMM", "0") == "1"
+
+
+def packed_bf16_enabled():
+    """bf16 inputs on the packed-weight kernels are opt-in (ASVD_PACKED_BF16=1, or `module.packed_bf16 = True` on one packed Linear or
+    SVDLinear): the kernels of csrc/w8_linear.hip in their bf16 form (K19), for a module whose weight_dtype and bias are bf16 as well, under the
+    token thresholds of the fp16 form.  Measured in one run only (profiles/w8_forward_bf16.json, DESIGN.md section 4 "K19"), hence still a
+    switch; off, a bf16 input keeps dequantize + F.linear."""
+    return os.environ.get("ASVD_PACKED_BF16", "0") == "1"
 
 
 class PackedLinear(nn.Module):
@@ -39,14 +51,23 @@ class PackedLinear(nn.Module):
                 setattr(self, n, old.to(new.device))
         return self
 
-    def _kernel_input(self, x, max_tokens):
-        """x as the contiguous 16-byte-aligned [tokens, in] fp16 matrix the forward kernels take, or None when this input goes through
-        dequantize + F.linear: not on the device, not fp16 (input, weight or bias), more than max_tokens tokens, under autograd, or code rows
-        that do not allow 16-byte loads"""
+    def _kernel_dtype_ok(self, x, bf16=None):
+        """input, weight and bias are ALL fp16, or ALL bf16 with the bf16 form switched on (`bf16`: the caller's own switch; None: this
+        module's, packed_bf16_enabled).  Mixed dtypes never take a kernel."""
+        dt = self.weight_dtype
+        if x.dtype != dt or (self.bias is not None and self.bias.dtype != dt):
+            return False
+        if dt == torch.bfloat16:
+            return bool(getattr(self, "packed_bf16", False) or packed_bf16_enabled()) if bf16 is None else bool(bf16)
+        return dt == torch.float16
+
+    def _kernel_input(self, x, max_tokens, bf16=None):
+        """x as the contiguous 16-byte-aligned [tokens, in] fp16 (or, switched on, bf16: _kernel_dtype_ok) matrix the forward kernels take, or
+        None when this input goes through dequantize + F.linear: not on the device, not of the kernels' dtype (input, weight or bias), more than
+        max_tokens tokens, under autograd, or code rows that do not allow 16-byte loads"""
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if not (x.is_cuda and x.dtype == torch.float16 and self.weight_dtype == torch.float16 and 0 < tokens <= max_tokens
-                and (self.bias is None or self.bias.dtype == torch.float16) and not (torch.is_grad_enabled() and x.requires_grad)
-                and self.kernel_rows_ok()):
+        if not (x.is_cuda and self._kernel_dtype_ok(x, bf16) and 0 < tokens <= max_tokens
+                and not (torch.is_grad_enabled() and x.requires_grad) and self.kernel_rows_ok()):
             return None
         x2d = x.reshape(-1, x.shape[-1])
         x2d = x2d if x2d.is_contiguous() else x2d.contiguous()

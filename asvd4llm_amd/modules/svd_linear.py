@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from .. import ops
 from .._lib import AsvdHipError
+from .packed_linear import packed_bf16_enabled
 from .w8_linear import W8Linear
 from .wb_linear import WBLinear
 
@@ -44,7 +45,9 @@ def _fused_forward_enabled():
 # The value is the packed kernels' own dispatch limit (W8_FORWARD_MAX_TOKENS / WB_FORWARD_MAX_TOKENS), not a crossover: MEASURED SLOWER than the two
 # launches at every token count (tools/bench_w8_forward.py --fused_pair --tokens 1,4,16 on MI355X, profiles/w8_fused_pair.json, DESIGN.md section 4,
 # K16: 1.51 / 1.70 / 1.92 of the two-launch time at 1 / 4 / 16 tokens in graph time at 8 bits per row, 1.39 / 1.55 / 1.76 at 4 bits with G = 128).  The
-# path claims no speed and stays opt-in; it gives the two-launch bits in one launch.
+# path claims no speed and stays opt-in; it gives the two-launch bits in one launch.  An all-bf16 pair (packed_linear.packed_bf16_enabled as
+# well) takes the same constant and is slower than its two launches too (--fused_pair --dtype bf16 --tokens 1,4,16, one run,
+# profiles/w8_forward_bf16.json: 1.51 / 1.71 / 1.95 of the two-launch time at 8 bits per row in graph time, the bits of the two launches).
 FUSED_PACKED_MAX_TOKENS = 16
 
 
@@ -389,7 +392,8 @@ class SVDLinear(nn.Module):
         replaces both factors' forward(), so it is taken only when that is all that would run and both would take their kernel: the switch is on,
         the factors are exactly two W8Linear or two WBLinear of one storage width and one group size, BLinear has no bias, nothing is hooked on
         (the factors or the module registry: calibration hooks of a compressed model keep running), and the conditions of both factors'
-        _kernel_input hold up to FUSED_PACKED_MAX_TOKENS tokens."""
+        _kernel_input hold up to FUSED_PACKED_MAX_TOKENS tokens.  The dtypes are all fp16, or all bf16 with the bf16 kernels switched on as
+        well (_pair_bf16_enabled); every other combination is "not fp16"."""
         A, B = self.ALinear, self.BLinear
         if not (getattr(self, "fused_packed", False) or _fused_packed_enabled()):
             return "switched off"
@@ -406,8 +410,8 @@ class SVDLinear(nn.Module):
         tokens = inp.numel() // inp.shape[-1] if inp.shape[-1] else 0
         if not 0 < tokens <= FUSED_PACKED_MAX_TOKENS:
             return "token count"
-        if not (inp.dtype == torch.float16 and A.weight_dtype == torch.float16 and B.weight_dtype == torch.float16
-                and (A.bias is None or A.bias.dtype == torch.float16)):
+        dt = torch.bfloat16 if inp.dtype == torch.bfloat16 and self._pair_bf16_enabled() else torch.float16
+        if not (inp.dtype == dt and A.weight_dtype == dt and B.weight_dtype == dt and (A.bias is None or A.bias.dtype == dt)):
             return "not fp16"
         if inp.shape[-1] != B.in_features or A.in_features != B.out_features:
             return "shapes"
@@ -418,6 +422,12 @@ class SVDLinear(nn.Module):
         if not (inp.is_cuda and A.scales.device == inp.device and B.scales.device == inp.device):
             return "not on the device"
         return None
+
+    def _pair_bf16_enabled(self):
+        """the bf16 form of the packed kernels (K19) is switched on for this pair: ASVD_PACKED_BF16=1, `packed_bf16 = True` on this module, or
+        on both factors"""
+        return bool(getattr(self, "packed_bf16", False) or packed_bf16_enabled()
+                    or (getattr(self.ALinear, "packed_bf16", False) and getattr(self.BLinear, "packed_bf16", False)))
 
     def _fused_packed_work(self, x2d):
         """ONE barrier / intermediate workspace per stream (two launches in flight must not share barrier words), created on first use"""
@@ -467,11 +477,12 @@ class SVDLinear(nn.Module):
         # returns the bits of the two calls below (K16, csrc/w8_linear.hip); fused_packed_refusal has the conditions
         if self.fused_packed_refusal(inp) is None:
             A, B = self.ALinear, self.BLinear
-            x2d = B._kernel_input(inp, FUSED_PACKED_MAX_TOKENS)   # None: a misaligned view
+            x2d = B._kernel_input(inp, FUSED_PACKED_MAX_TOKENS, bf16=True)   # None: a misaligned view (the refusal has checked the dtypes)
             if x2d is not None:
                 wb = type(B) is WBLinear
                 y = ops.lowrank_packed_forward(x2d, B.qbits if wb else B.qweight, B.scales, B.zeros, A.qbits if wb else A.qweight, A.scales, A.zeros,
-                                               _storage_bits(B), A.bias, self._fused_packed_work(x2d), group_size=B.group_size)
+                                               _storage_bits(B), A.bias, self._fused_packed_work(x2d), group_size=B.group_size,
+                                               weight_dtype=B.weight_dtype)
                 return y.view(*inp.shape[:-1], A.out_features)
         y = self.BLinear(inp)
         y = self.ALinear(y)

@@ -2,7 +2,8 @@
 
 The weight it stands for is  w[n, k] = (scales[n] * (qweight[n, k] - zeros[n])).to(weight_dtype),  the value the fake quantizer
 (quantization.rtn_quant_sequential) writes into an nn.Linear, bit for bit.  Decode-sized fp16 inputs run on the W8A16 kernel of
-csrc/w8_linear.hip, which dequantizes to exactly that value in registers; every other input dequantizes the layer's weight into a temporary
+csrc/w8_linear.hip, which dequantizes to exactly that value in registers (bf16 inputs of a bf16 module too once ASVD_PACKED_BF16=1 or
+`packed_bf16 = True` switches them on, modules/packed_linear.py); every other input dequantizes the layer's weight into a temporary
 (csrc/w8_linear.hip as well) and calls F.linear on it, so the model's resident size stays packed.  Opt-in (ASVD_PACKED_GEMM=1 or `packed_gemm = True`,
 modules/packed_linear.py): fp16 inputs of 17 .. PACKED_GEMM_MAX_TOKENS tokens run on the token-tiled GEMM on the codes instead (K17), without the temporary.
 
@@ -24,6 +25,10 @@ from .packed_linear import PackedLinear
 # tokens on).  These figures hold for rows that allow 16-byte loads only: see W8Linear.kernel_rows_ok.
 # Layers with group-wise scales take the same constant: NOT MEASURED for grouped scales (the grouped kernel streams 8 bytes per group more;
 # tools/bench_w8_forward.py --group_size measures it next to the per-row pass on the same codes).
+# bf16 inputs (opt-in, packed_linear.packed_bf16_enabled) take the same constant.  Measured once for bf16 (--dtype bf16 --force_kernel --tokens
+# 1,4,16,32,64 of the same tool, one run, profiles/w8_forward_bf16.json): against bf16 nn.Linear on the fake-quantized weights the packed pass takes
+# 0.64 / 0.65 / 0.76 of the time at 1 / 4 / 16 tokens in graph time on the ASVD-0.9 set and 1.07 / 1.29 at 32 / 64 (plain set 0.60 / 0.61 / 0.69,
+# then 1.08 / 1.12), and 0.38 / 0.39 / 0.45 of dequantize + F.linear in bf16, the path a bf16 module takes with the switch off: the fp16 crossover.
 W8_FORWARD_MAX_TOKENS = 16
 
 
@@ -90,11 +95,12 @@ class W8Linear(PackedLinear):
     def forward(self, x):
         x2d = self._kernel_input(x, W8_FORWARD_MAX_TOKENS)
         if x2d is not None:
-            y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            y = ops.w8_linear(x2d, self.qweight, self.scales, self.zeros, self.bias, group_size=self.group_size, weight_dtype=self.weight_dtype)
             return y.view(*x.shape[:-1], self.out_features)
         x2d = self._gemm_input(x, W8_FORWARD_MAX_TOKENS)   # opt-in (packed_linear.packed_gemm_enabled): the GEMM on the codes, one per byte
         if x2d is not None:
-            y = ops.packed_gemm(x2d, self.qweight, 8, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            y = ops.packed_gemm(x2d, self.qweight, 8, self.scales, self.zeros, self.bias, group_size=self.group_size,
+                                weight_dtype=self.weight_dtype)
             return y.view(*x.shape[:-1], self.out_features)
         return self._dense_forward(x)
 

@@ -24,7 +24,10 @@ from .w8_linear import expand_groups, param_shape
 # Token count up to which forward() takes the kernel.  NOT MEASURED for this kernel: the value is W8_FORWARD_MAX_TOKENS (modules/w8_linear.py),
 # whose tile loop this kernel shares; tools/bench_w8_forward.py --code_bits 6 / 4 (with and without --force_kernel) measures WBLinear's own two
 # paths.  The figures hold for rows that allow 16-byte loads only: see WBLinear.kernel_rows_ok.  Layers with group-wise scales take the same
-# constant, NOT MEASURED for grouped scales either (--group_size of the same tool).
+# constant, NOT MEASURED for grouped scales either (--group_size of the same tool).  bf16 inputs (opt-in, packed_linear.packed_bf16_enabled) take
+# it too; measured once for bf16 at 4 bits with G = 128 (--dtype bf16 --code_bits 4 --group_size 128 --tokens 1,4,16, one run,
+# profiles/w8_forward_bf16.json): 0.46 / 0.47 / 0.54 of dequantize + F.linear in bf16 at 1 / 4 / 16 tokens in graph time on the ASVD-0.9 set (plain
+# set 0.40 / 0.43 / 0.51); larger token counts NOT MEASURED for this kernel in bf16 either.
 WB_FORWARD_MAX_TOKENS = 16
 
 WB_BITS = (4, 6)
@@ -123,11 +126,13 @@ class WBLinear(PackedLinear):
     def forward(self, x):
         x2d = self._kernel_input(x, WB_FORWARD_MAX_TOKENS)
         if x2d is not None:
-            y = ops.wb_linear(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            y = ops.wb_linear(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size,
+                              weight_dtype=self.weight_dtype)
             return y.view(*x.shape[:-1], self.out_features)
         x2d = self._gemm_input(x, WB_FORWARD_MAX_TOKENS)   # opt-in (packed_linear.packed_gemm_enabled): the GEMM on the bitstream rows
         if x2d is not None:
-            y = ops.packed_gemm(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size)
+            y = ops.packed_gemm(x2d, self.qbits, self.bits, self.scales, self.zeros, self.bias, group_size=self.group_size,
+                                weight_dtype=self.weight_dtype)
             return y.view(*x.shape[:-1], self.out_features)
         return self._dense_forward(x)
 

@@ -552,15 +552,31 @@ def rtn_quant(w, bits, want_params=False, group_size=0, mse=False, mse_norm=2.4,
 
 W8_MAX_TOKENS = 256  # ASVD_W8_MAX_TOKENS (asvd_w8_linear_max_tokens)
 
+ACT_DTYPES = (torch.float16, torch.bfloat16)   # activation types of the packed-weight forward kernels (K12 - K14, K16, K17; bf16: K19)
 
-def w8_linear(x2d, q, scale, zero, bias=None, group_size=0):
-    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (q - zero)) dequantized in registers (K12, asvd_w8_linear_f16): x2d [T <= 256, K] fp16
+
+def _act_dtype(what, x2d, bias, weight_dtype):
+    """the act_dtype argument of the asvd_*_a16 entries.  `weight_dtype` names the weight the codes stand for (a module passes
+    self.weight_dtype), and the kernels form that weight in registers: x, bias and y are of that dtype, fp16 or bf16.  Raises ValueError before
+    the library or the device is asked for."""
+    if weight_dtype not in ACT_DTYPES:
+        raise ValueError(f"{what}: weight_dtype must be torch.float16 or torch.bfloat16 (got {weight_dtype}); there is no fp32 forward kernel")
+    if x2d.dtype != weight_dtype or (bias is not None and bias.dtype != weight_dtype):
+        raise ValueError(f"{what} with weight_dtype={weight_dtype} needs x and bias of that dtype (got x {x2d.dtype}"
+                         + (f", bias {bias.dtype})" if bias is not None else ")"))
+    return _DT[weight_dtype]
+
+
+def w8_linear(x2d, q, scale, zero, bias=None, group_size=0, weight_dtype=torch.float16):
+    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (q - zero)) dequantized in registers (K12, asvd_w8_linear_a16): x2d [T <= 256, K] fp16
     contiguous, q [N, K] uint8 (unit column stride), scale / zero [N] fp32, bias [N] fp16 or None.  One launch, deterministic.
-    group_size 64 / 128 (K14, asvd_w8_linear_grouped_f16): scale / zero [N, ceil(K / group_size)]; K % 16 == 0 and 16-byte-aligned x and rows only."""
+    group_size 64 / 128 (K14): scale / zero [N, ceil(K / group_size)]; K % 16 == 0 and 16-byte-aligned x and rows only.
+    weight_dtype=torch.bfloat16 (K19): the same with bf16 for fp16 throughout (x, bias, y and the weight the codes stand for)."""
+    act = _act_dtype("w8_linear", x2d, bias, weight_dtype)
     lib = L.load(True)
     group = _group(group_size)
     _dev(x2d, "x")
-    if x2d.dim() != 2 or q.dim() != 2 or x2d.dtype != torch.float16 or q.dtype != torch.uint8 or not x2d.is_contiguous() or q.stride(1) != 1:
+    if x2d.dim() != 2 or q.dim() != 2 or x2d.dtype != weight_dtype or q.dtype != torch.uint8 or not x2d.is_contiguous() or q.stride(1) != 1:
         raise ValueError(f"w8_linear needs x [T, K] fp16 contiguous and q [N, K] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, {tuple(q.shape)} {q.dtype})")
     T, K = x2d.shape
     N = q.shape[0]
@@ -568,7 +584,7 @@ def w8_linear(x2d, q, scale, zero, bias=None, group_size=0):
         raise ValueError(f"w8_linear: x {tuple(x2d.shape)} against q {tuple(q.shape)}; 1 <= tokens <= {W8_MAX_TOKENS}")
     if scale.dtype != torch.float32 or zero.dtype != torch.float32 or (not group and (scale.numel() != N or zero.numel() != N)) \
             or not scale.is_contiguous() \
-            or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
+            or not zero.is_contiguous() or (bias is not None and (bias.dtype != weight_dtype or bias.numel() != N or not bias.is_contiguous())):
         raise ValueError("w8_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
     if q.device != x2d.device or scale.device != x2d.device or zero.device != x2d.device or (bias is not None and bias.device != x2d.device):
         raise ValueError("w8_linear: all tensors must live on the device of x")
@@ -576,15 +592,10 @@ def w8_linear(x2d, q, scale, zero, bias=None, group_size=0):
         _check_params("w8_linear", scale, zero, N, K, group, x2d.device)
         if K % 16 or x2d.data_ptr() % 16 or q.data_ptr() % 16 or q.stride(0) % 16:
             raise ValueError("w8_linear with group_size needs K % 16 == 0 and x and the rows of q 16-byte aligned")
-    y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
+    y = torch.empty((T, N), dtype=weight_dtype, device=x2d.device)
     with _on(x2d.device):
-        if group:
-            L.check(lib.asvd_w8_linear_grouped_f16(x2d.data_ptr(), T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), group,
-                                                   bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)),
-                    "asvd_w8_linear_grouped_f16")
-            return y
-        L.check(lib.asvd_w8_linear_f16(x2d.data_ptr(), T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_w8_linear_f16")
+        L.check(lib.asvd_w8_linear_a16(x2d.data_ptr(), act, T, q.data_ptr(), q.stride(0), scale.data_ptr(), zero.data_ptr(), group,
+                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_w8_linear_a16")
     return y
 
 
@@ -679,14 +690,15 @@ def wb_dequant(qbits, bits, cols, scale, zero, dtype, out=None, group_size=0):
     return out
 
 
-def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0):
-    """w8_linear on bitstream rows (K13, asvd_wb_linear_f16): x2d [T <= 256, K] fp16 contiguous, K % 16 == 0, qbits [N, wb_row_bytes(K, bits)]
+def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0, weight_dtype=torch.float16):
+    """w8_linear on bitstream rows (K13, asvd_wb_linear_a16): x2d [T <= 256, K] fp16 contiguous, K % 16 == 0, qbits [N, wb_row_bytes(K, bits)]
     uint8, scale / zero [N] fp32, bias [N] fp16 or None; x2d and the rows 16-byte aligned.  The bits of w8_linear on the same codes.
-    group_size 64 / 128 (K14, asvd_wb_linear_grouped_f16): scale / zero [N, ceil(K / group_size)]."""
+    group_size 64 / 128 (K14): scale / zero [N, ceil(K / group_size)].  weight_dtype=torch.bfloat16 (K19): bf16 for fp16 throughout."""
+    act = _act_dtype("wb_linear", x2d, bias, weight_dtype)
     lib = L.load(True)
     group = _group(group_size)
     _dev(x2d, "x")
-    if x2d.dim() != 2 or qbits.dim() != 2 or x2d.dtype != torch.float16 or qbits.dtype != torch.uint8 or not x2d.is_contiguous() or qbits.stride(1) != 1:
+    if x2d.dim() != 2 or qbits.dim() != 2 or x2d.dtype != weight_dtype or qbits.dtype != torch.uint8 or not x2d.is_contiguous() or qbits.stride(1) != 1:
         raise ValueError(f"wb_linear needs x [T, K] fp16 contiguous and qbits [N, row bytes] uint8 (got {tuple(x2d.shape)} {x2d.dtype}, "
                          f"{tuple(qbits.shape)} {qbits.dtype})")
     T, K = x2d.shape
@@ -695,7 +707,7 @@ def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0):
         raise ValueError(f"wb_linear: x {tuple(x2d.shape)} against qbits {tuple(qbits.shape)} of {bits}-bit codes; K % 16 == 0, 1 <= tokens <= {W8_MAX_TOKENS}")
     if scale.dtype != torch.float32 or zero.dtype != torch.float32 or (not group and (scale.numel() != N or zero.numel() != N)) \
             or not scale.is_contiguous() \
-            or not zero.is_contiguous() or (bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous())):
+            or not zero.is_contiguous() or (bias is not None and (bias.dtype != weight_dtype or bias.numel() != N or not bias.is_contiguous())):
         raise ValueError("wb_linear needs scale / zero [N] fp32 and bias [N] fp16 (or None), contiguous")
     if group:
         _check_params("wb_linear", scale, zero, N, K, group, scale.device)
@@ -703,15 +715,10 @@ def wb_linear(x2d, qbits, bits, scale, zero, bias=None, group_size=0):
         raise ValueError("wb_linear: all tensors must live on the device of x")
     if x2d.data_ptr() % 16 or qbits.data_ptr() % 16 or qbits.stride(0) % 16:
         raise ValueError("wb_linear needs x and the rows of qbits 16-byte aligned")
-    y = torch.empty((T, N), dtype=torch.float16, device=x2d.device)
+    y = torch.empty((T, N), dtype=weight_dtype, device=x2d.device)
     with _on(x2d.device):
-        if group:
-            L.check(lib.asvd_wb_linear_grouped_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
-                                                   group, bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)),
-                    "asvd_wb_linear_grouped_f16")
-            return y
-        L.check(lib.asvd_wb_linear_f16(x2d.data_ptr(), T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_wb_linear_f16")
+        L.check(lib.asvd_wb_linear_a16(x2d.data_ptr(), act, T, qbits.data_ptr(), qbits.stride(0), int(bits), scale.data_ptr(), zero.data_ptr(), group,
+                                       bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_wb_linear_a16")
     return y
 
 
@@ -720,18 +727,20 @@ def lowrank_packed_work(T, r, device):
     return torch.zeros(int(L.load().asvd_lowrank_packed_work_bytes(int(T), int(r))), dtype=torch.uint8, device=device)
 
 
-def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_zero, bits, bias, work, group_size=0):
-    """y = fp16(fp16(x wB^T) wA^T + bias) for a pair of packed factors in one launch (K16, asvd_lowrank_packed_f16): the bits of w8_linear /
+def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_zero, bits, bias, work, group_size=0, weight_dtype=torch.float16):
+    """y = fp16(fp16(x wB^T) wA^T + bias) for a pair of packed factors in one launch (K16, asvd_lowrank_packed_a16): the bits of w8_linear /
     wb_linear applied twice.  x2d [T <= 256, K] fp16 contiguous; bits is the STORAGE width of both factors: 8 (B_codes [r, K], A_codes [N, r]
     uint8, one code per byte) or 6 / 4 (bitstream rows [r, wb_row_bytes(K, bits)], [N, wb_row_bytes(r, bits)]); scale / zero fp32 [r] and [N],
     or with group_size 64 / 128 [r, ceil(K / G)] and [N, ceil(r / G)]; bias [N] fp16 or None; K % 16 == 0 and r % 16 == 0, x and the code rows
-    16-byte aligned; work from lowrank_packed_work(>= T, r), one per stream in flight."""
+    16-byte aligned; work from lowrank_packed_work(>= T, r), one per stream in flight.  weight_dtype=torch.bfloat16 (K19): bf16 for fp16
+    throughout, the intermediate included (the same workspace: 2 bytes per element)."""
+    act = _act_dtype("lowrank_packed_forward", x2d, bias, weight_dtype)
     lib = L.load(True)
     group, bits = _group(group_size), int(bits)
     _dev(x2d, "x")
     if bits not in (8, 6, 4):
         raise ValueError(f"lowrank_packed_forward: storage width 8, 6 or 4 bits (got {bits})")
-    if x2d.dim() != 2 or x2d.dtype != torch.float16 or not x2d.is_contiguous() or any(
+    if x2d.dim() != 2 or x2d.dtype != weight_dtype or not x2d.is_contiguous() or any(
             c.dim() != 2 or c.dtype != torch.uint8 or c.stride(1) != 1 for c in (B_codes, A_codes)):
         raise ValueError("lowrank_packed_forward needs x [T, K] fp16 contiguous and uint8 code matrices with unit column stride")
     T, K = x2d.shape
@@ -743,18 +752,18 @@ def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_ze
     dev = x2d.device
     _check_params("lowrank_packed_forward (B)", B_scale, B_zero, r, K, group, dev)
     _check_params("lowrank_packed_forward (A)", A_scale, A_zero, N, r, group, dev)
-    if bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
+    if bias is not None and (bias.dtype != weight_dtype or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
         raise ValueError("lowrank_packed_forward needs bias [N] fp16 contiguous on the device of x (or None)")
     if B_codes.device != dev or A_codes.device != dev or work.device != dev:
         raise ValueError("lowrank_packed_forward: all tensors must live on the device of x")
     if x2d.data_ptr() % 16 or B_codes.data_ptr() % 16 or A_codes.data_ptr() % 16 or B_codes.stride(0) % 16 or A_codes.stride(0) % 16:
         raise ValueError("lowrank_packed_forward needs x and the code rows 16-byte aligned")
-    y = torch.empty((T, N), dtype=torch.float16, device=dev)
+    y = torch.empty((T, N), dtype=weight_dtype, device=dev)
     with _on(dev):
-        L.check(lib.asvd_lowrank_packed_f16(x2d.data_ptr(), T, B_codes.data_ptr(), B_codes.stride(0), B_scale.data_ptr(), B_zero.data_ptr(),
+        L.check(lib.asvd_lowrank_packed_a16(x2d.data_ptr(), act, T, B_codes.data_ptr(), B_codes.stride(0), B_scale.data_ptr(), B_zero.data_ptr(),
                                             A_codes.data_ptr(), A_codes.stride(0), A_scale.data_ptr(), A_zero.data_ptr(), bits, group,
                                             bias.data_ptr() if bias is not None else None, N, K, r, y.data_ptr(), work.data_ptr(), work.numel(),
-                                            _stream(x2d)), "asvd_lowrank_packed_f16")
+                                            _stream(x2d)), "asvd_lowrank_packed_a16")
     _lowrank_count(work)   # the give-up word of the workspace: as lowrank_forward
     return y
 
@@ -762,17 +771,19 @@ def lowrank_packed_forward(x2d, B_codes, B_scale, B_zero, A_codes, A_scale, A_ze
 PACKED_GEMM_MAX_TOKENS = 1 << 20  # ASVD_PACKED_GEMM_MAX_TOKENS (asvd_packed_gemm_max_tokens)
 
 
-def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0):
-    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (code - zero)) for inputs beyond decode (K17, asvd_packed_gemm_f16): the token-tiled
+def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0, weight_dtype=torch.float16):
+    """y = fp16(x2d . w^T + bias) with w = fp16(scale * (code - zero)) for inputs beyond decode (K17, asvd_packed_gemm_a16): the token-tiled
     GEMM that stages x through LDS once per workgroup and streams the codes once per tile of up to 128 tokens.  x2d [T, K] fp16 contiguous,
     K % 16 == 0, 1 <= T <= PACKED_GEMM_MAX_TOKENS.  bits is the STORAGE width of `codes`: 8 (W8Linear.qweight: [N, K] uint8, unit column
     stride) or 6 / 4 (WBLinear.qbits: bitstream rows [N, wb_row_bytes(K, bits)]).  scale / zero [N] fp32, or with group_size 64 / 128
     [N, ceil(K / group_size)]; bias [N] fp16 or None; x2d and the code rows 16-byte aligned.  One launch, deterministic; the weight is the
-    one w8_dequant / wb_dequant write, bit for bit.  Every argument check comes before the device is asked for."""
+    one w8_dequant / wb_dequant write, bit for bit.  weight_dtype=torch.bfloat16 (K19): bf16 for fp16 throughout.  Every argument check comes
+    before the device is asked for."""
+    act = _act_dtype("packed_gemm", x2d, bias, weight_dtype)
     group, bits = _group(group_size), int(bits)
     if bits not in (8, 6, 4):
         raise ValueError(f"packed_gemm: storage width 8, 6 or 4 bits (got {bits})")
-    if x2d.dim() != 2 or codes.dim() != 2 or x2d.dtype != torch.float16 or codes.dtype != torch.uint8 or not x2d.is_contiguous() or codes.stride(1) != 1:
+    if x2d.dim() != 2 or codes.dim() != 2 or x2d.dtype != weight_dtype or codes.dtype != torch.uint8 or not x2d.is_contiguous() or codes.stride(1) != 1:
         raise ValueError(f"packed_gemm needs x [T, K] fp16 contiguous and codes [N, row bytes] uint8 with unit column stride (got {tuple(x2d.shape)} "
                          f"{x2d.dtype}, {tuple(codes.shape)} {codes.dtype})")
     T, K = x2d.shape
@@ -782,7 +793,7 @@ def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0):
                          f"1 <= tokens <= {PACKED_GEMM_MAX_TOKENS}")
     dev = x2d.device
     _check_params("packed_gemm", scale, zero, N, K, group, dev)
-    if bias is not None and (bias.dtype != torch.float16 or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
+    if bias is not None and (bias.dtype != weight_dtype or bias.numel() != N or not bias.is_contiguous() or bias.device != dev):
         raise ValueError("packed_gemm needs bias [N] fp16 contiguous on the device of x (or None)")
     if codes.device != dev:
         raise ValueError("packed_gemm: all tensors must live on the device of x")
@@ -790,10 +801,10 @@ def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0):
         raise ValueError("packed_gemm needs x and the code rows 16-byte aligned")
     _dev(x2d, "x")
     lib = L.load(True)
-    y = torch.empty((T, N), dtype=torch.float16, device=dev)
+    y = torch.empty((T, N), dtype=weight_dtype, device=dev)
     with _on(dev):
-        L.check(lib.asvd_packed_gemm_f16(x2d.data_ptr(), T, codes.data_ptr(), codes.stride(0), bits, scale.data_ptr(), zero.data_ptr(), group,
-                                         bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_packed_gemm_f16")
+        L.check(lib.asvd_packed_gemm_a16(x2d.data_ptr(), act, T, codes.data_ptr(), codes.stride(0), bits, scale.data_ptr(), zero.data_ptr(), group,
+                                         bias.data_ptr() if bias is not None else None, N, K, y.data_ptr(), _stream(x2d)), "asvd_packed_gemm_a16")
     return y
 
 

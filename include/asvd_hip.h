@@ -450,6 +450,28 @@ int asvd_packed_gemm_f16(const void* x, int64_t T, const void* q, int64_t ld_byt
                          const void* bias, int64_t N, int64_t K, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K19  bf16 activations on the packed-weight kernels: K12 / K13 / K14, K16 and K17 with the activation dtype and the group size as arguments.
+ *   act_dtype: ASVD_F16 or ASVD_BF16, the type of x, bias, y (and of the intermediate z of the pair) AND of the weight the codes stand for:
+ *        y[T, N] = act( x[T, K] . w^T + bias ),   w[n, k] = act( scale * (code - zero) )
+ *   Anything else (ASVD_F32 included) returns ASVD_E_BADARG before any device call.  With ASVD_F16 every entry IS its _f16 counterpart (those
+ *   forward here) and returns its bits.  With ASVD_BF16 the kernels differ in four places and nowhere else: w is the fp32 value rounded ONCE
+ *   (RNE) to bf16, the bits asvd_w8_dequant / asvd_wb_dequant write with out_dtype ASVD_BF16 for finite values; the matrix instruction is the
+ *   bf16 one on the same operands (the same tiles, k permutation, split of k over the waves and order of every fp32 sum); the bias is read
+ *   as bf16; y (and z) are rounded RNE to bf16.  A pair that gives up at its barrier overwrites y with bf16 NaNs.
+ *   group: 0 (scale, zero per row), 64 or 128 (per group of that many columns), as in the _grouped_f16 entries; other values ASVD_E_BADARG.
+ *   Every other argument rule (token limits, alignment, leading dimensions, workspace) is that of the _f16 entry of the same name;
+ *   asvd_lowrank_packed_work_bytes holds for both dtypes (2 bytes per element of z).  Deterministic, asynchronous. */
+int asvd_w8_linear_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ldq, const float* scale, const float* zero, int64_t group,
+                       const void* bias, int64_t N, int64_t K, void* y, void* stream);
+int asvd_wb_linear_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                       int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream);
+int asvd_packed_gemm_a16(const void* x, int act_dtype, int64_t T, const void* q, int64_t ld_bytes, int bits, const float* scale, const float* zero,
+                         int64_t group, const void* bias, int64_t N, int64_t K, void* y, void* stream);
+int asvd_lowrank_packed_a16(const void* x, int act_dtype, int64_t T, const void* qB, int64_t ldB, const float* scaleB, const float* zeroB,
+                            const void* qA, int64_t ldA, const float* scaleA, const float* zeroA, int bits, int64_t group, const void* bias,
+                            int64_t N, int64_t K, int64_t r, void* y, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * C1  collective for the one exchange step of the multi-GPU path: all-gather of the per-layer sensitivities over
  * RCCL (xGMI).  The reference has no distributed path; a maintainer who binds only this library gets the collective here, the
  * Python host side uses torch.distributed (same RCCL) for it.  RCCL is resolved at run time from the process (torch's

@@ -33,7 +33,12 @@ modules of the narrowest path above.  Per shape set and token count it times thr
   (h) the dense path, dequantize + F.linear (PackedLinear._dense_forward: what the modules do for these inputs with the switch off),
   (a) nn.Linear on the resident fake-quantized fp16 weights (context only: it keeps two to four times the memory),
 and reports `gemm_over_dense`, whether (g) is not slower than (h) by more than (h)'s spread, (g)'s algorithmic GB/s and TFLOP/s, the largest
-N K 2-byte temporary (h) allocates per layer, and the largest difference of (g) from (a)."""
+N K 2-byte temporary (h) allocates per layer, and the largest difference of (g) from (a).
+--dtype bf16 (with any of the above) builds every weight, module and input in bf16 and switches the bf16 form of the kernels on (K19,
+packed_bf16 on every packed module and pair): (a) is then bf16 nn.Linear on the fake-quantized bf16 weights.  Without --gemm it adds
+  (f) dequantize + F.linear in bf16 on the modules of the narrowest path (PackedLinear._dense_forward: what a bf16 module does with the switch off),
+timed in the same alternation and reported under "dense_path" with `narrowest_over_dense`, the narrowest packed pass's time over it.  The keys
+keep their names ("fp16_linear" is the nn.Linear pass in --dtype); the output carries "dtype": "bf16".  Without --dtype the output is what it was."""
 import argparse
 import json
 import os
@@ -52,6 +57,18 @@ from asvd4llm_amd.modules import wb_linear as WB  # noqa: E402
 from bench_rtn import HBM_SPEC, median, shape_sets  # noqa: E402
 
 TOKENS = (1, 4, 16, 64)
+DT = torch.float16   # --dtype: the dtype of weights, modules and inputs
+
+
+class DensePath(nn.Module):
+    """path (f): dequantize + F.linear on a packed module, whatever its forward() dispatches"""
+
+    def __init__(self, mod):
+        super().__init__()
+        self.mod = mod
+
+    def forward(self, x):
+        return self.mod._dense_forward(x)
 
 
 def fused_pair_of(b_mod, a_mod):
@@ -59,35 +76,41 @@ def fused_pair_of(b_mod, a_mod):
     m = S.SVDLinear.__new__(S.SVDLinear)
     nn.Module.__init__(m)
     m.BLinear, m.ALinear, m.truncation_rank, m.fused_packed = b_mod, a_mod, b_mod.out_features, True
+    m.packed_bf16 = DT == torch.bfloat16
     return m
 
 
-def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0, fused_pair=False):
+def build_set(blocks, factored, bits, dev, seed, bitpacked=False, group=0, fused_pair=False, dense=False):
     """per block a list of layers; a layer is a list of (fp16 nn.Linear, W8Linear[, WBLinear]) stages applied in order (BLinear, ALinear for a
     factored layer: bench_rtn lists them as ALinear [out, r], BLinear [r, in])"""
     g = torch.Generator(device=dev).manual_seed(seed)
     out = []
     for blk in blocks:
-        ws = [(torch.randn(m, n, generator=g, device=dev, dtype=torch.float32) * 0.02).half() for m, n in blk]
+        ws = [(torch.randn(m, n, generator=g, device=dev, dtype=torch.float32) * 0.02).to(DT) for m, n in blk]
         res = ops.rtn_quant_batched(ws, bits, want_params=True)
         stages = []
         for fake, q, scale, zero, flagged in res:
             assert not flagged
             lin = nn.Linear(fake.shape[1], fake.shape[0], bias=False, device="meta")
             lin.weight = nn.Parameter(fake, requires_grad=False)
-            stage = (lin, W.W8Linear.from_codes(q, scale, zero, None, bits, torch.float16))
+            stage = (lin, W.W8Linear.from_codes(q, scale, zero, None, bits, DT))
             if bitpacked:
-                stage += (WB.WBLinear.from_codes(q, scale, zero, None, bits, torch.float16),)
+                stage += (WB.WBLinear.from_codes(q, scale, zero, None, bits, DT),)
             if group:   # the per-row pair of every row, once per group: the same weights on the same code buffer
                 ng = ops.n_groups(q.shape[1], group)
                 gs, gz = scale[:, None].expand(-1, ng).contiguous(), zero[:, None].expand(-1, ng).contiguous()
-                stage += ((WB.WBLinear.from_bits(stage[2].qbits, q.shape[1], gs, gz, None, bits, torch.float16, group_size=group),) if bitpacked
-                          else (W.W8Linear.from_codes(q, gs, gz, None, bits, torch.float16, group_size=group),))
+                stage += ((WB.WBLinear.from_bits(stage[2].qbits, q.shape[1], gs, gz, None, bits, DT, group_size=group),) if bitpacked
+                          else (W.W8Linear.from_codes(q, gs, gz, None, bits, DT, group_size=group),))
+            for mod in stage[1:]:
+                mod.packed_bf16 = DT == torch.bfloat16
             stages.append(stage)
+        narrow = 1 + bool(bitpacked) + bool(group)   # index of the narrowest packed path
         if fused_pair and factored:   # path (e) sits in the BLinear stage and maps x to y; the ALinear stage passes it on
             for i in range(0, len(stages), 2):
                 stages[i + 1] += (fused_pair_of(stages[i + 1][-1], stages[i][-1]),)
                 stages[i] += (nn.Identity(),)
+        if dense:
+            stages = [s + (DensePath(s[narrow]),) for s in stages]
         out.append([[stages[i + 1], stages[i]] for i in range(0, len(stages), 2)] if factored else [[s] for s in stages])
     return out
 
@@ -197,7 +220,7 @@ def run_set_gemm(blocks, factored, args, dev):
            "largest_dense_temporary_bytes": max(2 * s[0].weight.numel() for s in stages), "tokens": {}}
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
     for T in args.tokens:
-        xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
+        xs = {k: torch.randn(T, k, generator=g, device=dev).to(DT) for k in {layer[0][0].in_features for blk in layers for layer in blk}}
         launched, real = [], ops.packed_gemm
         ops.packed_gemm = lambda *a, **k: (launched.append(1), real(*a, **k))[1]
         run_pass_fn(layers, xs, lambda s: s[-1])
@@ -232,11 +255,13 @@ def stats(ts):
 def run_set(blocks, factored, args, dev):
     bitpacked = args.code_bits != 8
     fused = bool(args.fused_pair and factored)
-    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size, fused)
+    dense = args.dtype == "bf16"
+    layers = build_set(blocks, factored, args.bits, dev, args.seed, bitpacked, args.group_size, fused, dense)
     base_path = 2 if bitpacked else 1                       # the per-row pass (d) is compared with
-    npaths = 2 + bitpacked + bool(args.group_size) + fused
+    npaths = 2 + bitpacked + bool(args.group_size) + fused + dense
     grp_path = 1 + bitpacked + bool(args.group_size)        # (d) when it runs
-    two_path = npaths - 2                                   # the two-launch pass of the modules (e) fuses
+    two_path = grp_path                                     # the narrowest packed pass: the two-launch pass of the modules (e) fuses
+    fused_path, dense_path = two_path + 1, npaths - 1       # (e) and (f) when they run
     stages = [s for blk in layers for layer in blk for s in layer]
     code_bytes = sum(s[1].qweight.numel() + 8 * s[1].out_features for s in stages)
     fp16_bytes = sum(2 * s[0].weight.numel() for s in stages)
@@ -250,7 +275,7 @@ def run_set(blocks, factored, args, dev):
         res.update({"grouped_weight_bytes": grp_bytes, "grouped_extra_byte_share": round(grp_bytes / base_bytes - 1, 4)})
     g = torch.Generator(device=dev).manual_seed(args.seed + 1)
     for T in args.tokens:
-        xs = {k: torch.randn(T, k, generator=g, device=dev).half() for k in {layer[0][0].in_features for blk in layers for layer in blk}}
+        xs = {k: torch.randn(T, k, generator=g, device=dev).to(DT) for k in {layer[0][0].in_features for blk in layers for layer in blk}}
         act_bytes = sum(2 * T * (s[0].in_features + s[0].out_features) for s in stages)
         nbytes = code_bytes + act_bytes
         diff, top = max_difference(layers, xs)
@@ -285,18 +310,22 @@ def run_set(blocks, factored, args, dev):
                                   "grouped_gbps": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / 1e9, 1),
                                   "grouped_frac_of_hbm_spec": round((grp_bytes + act_bytes) / (d["median_ms"] * 1e-3) / HBM_SPEC, 4)})
             if fused:   # against the two launches per pair of the same modules; that pass's spread is the noise floor
-                two, e = stats(times[two_path]), stats(times[-1])
+                two, e = stats(times[two_path]), stats(times[fused_path])
                 rec[mode].update({"fused_pair": e, "two_launch": two, "fused_over_two_launch": round(e["median_ms"] / two["median_ms"], 4),
                                   "fused_minus_two_launch_ms": round(e["median_ms"] - two["median_ms"], 4),
                                   "two_launch_spread_ms": two["spread_ms"],
                                   "fused_faster_by_more_than_spread": e["median_ms"] < two["median_ms"] - two["spread_ms"]})
+            if dense:   # (f): what a bf16 module does with the switch off; its spread is the noise floor
+                nar, f = stats(times[two_path]), stats(times[dense_path])
+                rec[mode].update({"dense_path": f, "narrowest_over_dense": round(nar["median_ms"] / f["median_ms"], 4),
+                                  "narrowest_not_slower_than_dense": nar["median_ms"] <= f["median_ms"] + f["spread_ms"]})
         if args.group_size:
             diff_d, _ = max_difference(layers, xs, grp_path)
             same_bits = all(torch.equal(run_pass([[layer]], xs, grp_path), run_pass([[layer]], xs, base_path)) for layer in layers[0])
             rec.update({"grouped_max_rel_diff": diff_d / top if top else 0.0, "grouped_bits_equal_per_row_block0": same_bits})
         if fused:
-            rec["fused_pair_dispatched"] = all(layer[0][-1].fused_packed_refusal(xs[layer[0][0].in_features]) is None for blk in layers for layer in blk)
-            rec["fused_pair_bits_equal_two_launch"] = all(torch.equal(run_pass([[layer]], xs, npaths - 1), run_pass([[layer]], xs, two_path))
+            rec["fused_pair_dispatched"] = all(layer[0][fused_path].fused_packed_refusal(xs[layer[0][0].in_features]) is None for blk in layers for layer in blk)
+            rec["fused_pair_bits_equal_two_launch"] = all(torch.equal(run_pass([[layer]], xs, fused_path), run_pass([[layer]], xs, two_path))
                                                           for blk in layers for layer in blk)
         res["tokens"][str(T)] = rec
     return res
@@ -313,6 +342,8 @@ def main():
                     help="ASVD shape set only: add path (e), every factor pair of the narrowest packed path in one launch (K16), next to its two launches")
     ap.add_argument("--gemm", action="store_true",
                     help="measure the token-tiled GEMM on the codes (K17) against dequantize + F.linear and fp16 nn.Linear at --tokens (default 32 .. 2048)")
+    ap.add_argument("--dtype", type=str, default="fp16", choices=["fp16", "bf16"],
+                    help="bf16: weights, modules and inputs in bf16 on the bf16 form of the kernels (K19, packed_bf16 on); adds the dense path (f)")
     ap.add_argument("--blocks", type=int, default=0, help="--gemm: decoder blocks per shape set (0: all 32)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -337,6 +368,8 @@ def main():
         ap.error("--force_kernel with --group_size needs --rank_align to be a multiple of 16: the grouped kernels take K % 16 == 0 only")
     L.load(require_device=True)
     dev = torch.device("cuda", 0)
+    global DT
+    DT = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     if args.force_kernel:
         W.W8_FORWARD_MAX_TOKENS = ops.W8_MAX_TOKENS
         W.W8Linear.kernel_rows_ok = lambda self: True   # rows that allow no 16-byte loads too (--rank_align 1)
@@ -347,6 +380,8 @@ def main():
         P.PACKED_GEMM_MAX_TOKENS = ops.PACKED_GEMM_MAX_TOKENS   # measure the kernel at every token count, whatever forward() dispatches
         res = {"metric": "w8_gemm", "bits": args.bits, "iters": args.iters, "warmup": args.warmup, "rank_align": args.rank_align,
                "timing": "graph replay, device events", "sets": {}}
+        if args.dtype != "fp16":
+            res["dtype"] = args.dtype
         for name, blocks in shape_sets(0.9, args.rank_align).items():
             res["sets"][name] = run_set_gemm(blocks[:args.blocks] if args.blocks else blocks, "asvd" in name, args, dev)
             torch.cuda.empty_cache()
@@ -354,6 +389,8 @@ def main():
         return
     res = {"metric": "w8_forward", "bits": args.bits, "hbm_spec_Bps": HBM_SPEC, "iters": args.iters, "warmup": args.warmup,
            "dispatch_max_tokens": W.W8_FORWARD_MAX_TOKENS, "force_kernel": bool(args.force_kernel), "rank_align": args.rank_align, "sets": {}}
+    if args.dtype != "fp16":
+        res["dtype"] = args.dtype
     if args.group_size:
         res["group_size"] = args.group_size
     if args.code_bits != 8:
