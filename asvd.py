@@ -73,6 +73,34 @@ def run_weight_quant(model, args):
     rtn_quant_sequential(model, bits, **kw)
 
 
+def run_kv_cache_decode(model, calib_loader, args):
+    """--kv_cache_decode_tokens N: what the compressed k_proj / v_proj buy at run time.  Prints the bytes one token occupies in the ordinary
+    and in the low-rank KV cache (all layers), then greedy-decodes N tokens from the first calibration sample on both caches (K20 on the low-rank
+    one, asvd4llm_amd/kv_cache.py) and prints the largest difference of their logits."""
+    from asvd4llm_amd.kv_cache import greedy_decode, is_llama_family, kv_ranks
+    dense = 0
+    ranks = {}
+    for name, m in model.named_modules():
+        if name.endswith(("k_proj", "v_proj")):
+            width = m.ALinear.out_features if hasattr(m, "ALinear") else m.out_features
+            dense += 2 * width
+            ranks.setdefault(name.rsplit(".", 1)[0], []).append(m.BLinear.out_features if hasattr(m, "BLinear") else width)
+    ranks = kv_ranks(model) if is_llama_family(model) else [tuple(v) for v in ranks.values()]   # the runner's cache: what is realised
+    low = 2 * sum(sum(r) for r in ranks)
+    print(f"kv cache ranks (k, v) per layer: {ranks}")
+    print(f"kv cache bytes per token: dense {dense}, low-rank {low} (ratio {low / max(dense, 1):.4f})")
+    if not is_llama_family(model):
+        print("kv cache decode: the greedy runner serves Llama-family models only; this model is served at the LowRankKVAttention level")
+        return
+    ids = calib_loader[0]["input_ids"][:, :64].to(next(model.parameters()).device)
+    n = int(args.kv_cache_decode_tokens)
+    toks_low, logits_low = greedy_decode(model, ids, n, cache="lowrank")
+    toks_dense, logits_dense = greedy_decode(model, ids, n, cache="dense", forced=toks_low)
+    diff = (logits_low.float() - logits_dense.float()).abs().max().item()
+    print(f"kv cache decode: {n} tokens, largest logit difference {diff:.4e} (largest logit {logits_dense.float().abs().max().item():.4e}), "
+          f"tokens equal: {bool((toks_low == toks_dense).all())}")
+
+
 def main(args):
     check_weight_quant_args(args)
     np.random.seed(args.seed)
@@ -112,6 +140,9 @@ def main(args):
 
         if args.weight_quant != "none":
             run_weight_quant(model, args)
+
+        if getattr(args, "kv_cache_decode_tokens", 0) > 0 and (not args.dist or int(os.environ.get("RANK", "0")) == 0):
+            run_kv_cache_decode(model, calib_loader, args)
 
         if args.save_repo and (not args.dist or int(os.environ.get("RANK", "0")) == 0):
             # exported-repo layout of huggingface_repos/build_asvd_repo.py:58-92 (truncation_ranks + ALinear/BLinear keys)
@@ -188,6 +219,10 @@ def build_parser():
                         help="re-orthonormalise the long side's singular vectors after every factorisation (K18: U = W V / sigma loses orthogonality on "
                              "graded spectra, 2e-3 .. 2.5e-2 measured); matters under --sigma_fuse U / V, where one emitted factor is the raw vector "
                              "matrix.  Off by default; ASVD_SVD_ORTHO=1 is the environment switch of the library")
+    parser.add_argument("--kv_cache_decode_tokens", type=int, default=0,
+                        help="after the compression print the bytes per token of the ordinary and of the low-rank KV cache (k_proj / v_proj kept as "
+                             "their r-wide BLinear outputs) and greedy-decode this many tokens on both (Llama-family models; the low-rank cache runs "
+                             "the K20 decode-attention kernel where it serves the shape).  0 (default): nothing happens")
     parser.add_argument("--exclude_lm_head", action="store_true", help="do not hook/sweep/compress lm_head (the reference includes it)")
     parser.add_argument("--save_repo", type=str, default="", help="write the compressed model in the exported HF-repo layout of the reference (truncation_ranks in config.json)")
     parser.add_argument("--no_fused_sweep", dest="fused_sweep", action="store_false",

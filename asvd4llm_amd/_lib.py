@@ -12,6 +12,7 @@ F32, F16, BF16 = 0, 1, 2
 FUSE = {"UV": 0, "U": 1, "V": 2}
 STAT_ABS_MEAN, STAT_ABS_MAX, STAT_SQ_MEAN = 0, 1, 2
 PATH_REDUCED, PATH_REDUCE_FALLBACK, PATH_PLAIN_RETRY, PATH_SPLIT, PATH_SPLIT_REFUSED, PATH_GRAM_RETRY = 1, 2, 4, 8, 16, 32
+KV_ROPE_NONE, KV_ROPE_HALF = 0, 1
 OK, E_BADARG, E_WORKSPACE, E_HIP, E_NODEVICE, N_NOCONV, N_NAN = 0, -1, -2, -3, -4, 1, 2
 
 _c = ctypes
@@ -76,6 +77,11 @@ SIGNATURES = {
     "asvd_packed_gemm_a16": (_i, [_vp, _i, _i64, _vp, _i64, _i, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "asvd_lowrank_packed_a16": (_i, [_vp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _sz,
                                      _vp]),
+    "asvd_lowrank_kv_plan": (_i, [_i64, _i64, _i64, _c.POINTER(_i64), _c.POINTER(_i64), _c.POINTER(_i64)]),
+    "asvd_lowrank_kv_worksize": (_i, [_i64, _i64, _i64, _i64, _i64, _c.POINTER(_sz)]),
+    "asvd_lowrank_kv_scores": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "asvd_lowrank_kv_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                    _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_fro_worksize":(_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

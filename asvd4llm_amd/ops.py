@@ -808,6 +808,119 @@ def packed_gemm(x2d, codes, bits, scale, zero, bias=None, group_size=0, weight_d
     return y
 
 
+# ---- K20: decode attention on a low-rank KV cache (csrc/lowrank_kv.hip) ----------------------------------------------------------------
+
+KV_ROPE = {"none": L.KV_ROPE_NONE, "half": L.KV_ROPE_HALF}
+
+
+def rope_table(Tmax, D, theta=10000.0, device=None):
+    """(cos, sin) fp32 [Tmax, D/2] of the rotary embedding: angle(t, i) = t * theta^(-2i / D), the HF Llama inverse frequencies.  Row t rotates
+    position t; lowrank_kv_scores / lowrank_kv_decode apply it to the pairs (i, i + D/2) (rotate_half)."""
+    if D < 2 or D % 2 or Tmax < 1:
+        raise ValueError(f"rope_table: Tmax >= 1 and an even D (got {Tmax}, {D})")
+    inv = 1.0 / (float(theta) ** (torch.arange(0, D, 2, dtype=torch.int64, device=device).float() / D))
+    ang = torch.arange(Tmax, dtype=torch.int64, device=device).float()[:, None] * inv[None, :]
+    return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+def lowrank_kv_plan(B, H, Tmax):
+    """(token tile of the score kernels, split length, number of splits) K20 uses for (B, H, Tmax): host only"""
+    tile, split, n = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    L.check(L.load(False).asvd_lowrank_kv_plan(B, H, Tmax, ctypes.byref(tile), ctypes.byref(split), ctypes.byref(n)), "asvd_lowrank_kv_plan")
+    return tile.value, split.value, n.value
+
+
+def lowrank_kv_work(B, H, Tmax, r_k, r_v, device):
+    """the workspace of one K20 call at these sizes (uint8, reusable across steps; one per stream)"""
+    nb = ctypes.c_size_t()
+    L.check(L.load(False).asvd_lowrank_kv_worksize(B, H, Tmax, r_k, r_v, ctypes.byref(nb)), "asvd_lowrank_kv_worksize")
+    return _work(nb.value, device)
+
+
+def _kv_cache_arg(name, c, B, dev):
+    if c.dim() != 3 or c.dtype != torch.float16 or c.shape[0] != B or c.stride(2) != 1 or c.device != dev:
+        raise ValueError(f"{name}: cache [B, Tmax, r] fp16 with unit rank stride on the device of q (got {tuple(c.shape)} {c.dtype})")
+    r = c.shape[2]
+    if r < 16 or r % 16:
+        raise ValueError(f"{name}: rank {r} is not a multiple of 16")
+    if c.data_ptr() % 16 or c.stride(1) % 8 or c.stride(0) % 8 or c.stride(1) < r:
+        raise ValueError(f"{name}: rows must be 16-byte aligned (row stride {c.stride(1)}, batch stride {c.stride(0)} elements)")
+    return r
+
+
+def _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv):
+    if q.dim() != 3 or q.dtype != torch.float16 or not q.is_contiguous():
+        raise ValueError(f"{name} needs q [B, H, D] fp16 contiguous (got {tuple(q.shape)} {q.dtype})")
+    B, H, D = q.shape
+    dev = q.device
+    if D not in (64, 128) or H < 1 or H_kv < 1 or H % H_kv:
+        raise ValueError(f"{name}: head size 64 or 128 and H_kv dividing H (got D {D}, H {H}, H_kv {H_kv})")
+    r_k = _kv_cache_arg(name, ck, B, dev)
+    Tmax = ck.shape[1]
+    if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous() or lens.device != dev:
+        raise ValueError(f"{name} needs lens int32 [B] on the device of q")
+    if Ak.dtype != torch.float16 or tuple(Ak.shape) != (H_kv * D, r_k) or not Ak.is_contiguous() or Ak.device != dev or Ak.data_ptr() % 16:
+        raise ValueError(f"{name} needs Ak [H_kv * D, r_k] fp16 contiguous (got {tuple(Ak.shape)} {Ak.dtype})")
+    if bk is not None and (bk.dtype != torch.float16 or bk.numel() != H_kv * D or not bk.is_contiguous() or bk.device != dev):
+        raise ValueError(f"{name} needs bk [H_kv * D] fp16 contiguous or None")
+    mode, cos, sin = "none", None, None
+    if rope is not None:
+        mode, (cos, sin) = "half", rope
+        if bk is not None:
+            raise ValueError(f"{name}: a key bias cannot be combined with a rotation")
+        for t in (cos, sin):
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < Tmax or t.shape[1] != D // 2 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{name} needs cos / sin fp32 [>= Tmax, D/2] contiguous on the device of q")
+    return B, H, D, r_k, Tmax, mode, cos, sin
+
+
+def lowrank_kv_scores(q, ck, lens, Ak, H_kv, scale, bk=None, rope=None, work=None):
+    """S [B, H, Tmax] fp32 = scale * q_h . K_h[t] with K_h = C_k A_k[kv(h)]^T (rotated by rope = (cos, sin) tables when given), zeros at
+    t >= lens[b] (K20 stages a and b, asvd_lowrank_kv_scores).  q [B, H, D] fp16 (already rotated), ck [B, Tmax, r_k] fp16 (strided views with
+    16-byte aligned rows are fine), lens int32 [B], Ak [H_kv * D, r_k] fp16.  Every argument check comes before the device is asked for."""
+    B, H, D, r_k, Tmax, mode, cos, sin = _kv_args("lowrank_kv_scores", q, ck, lens, Ak, bk, rope, H_kv)
+    _dev(q, "q")
+    lib = L.load(True)
+    dev = q.device
+    if work is None:
+        work = lowrank_kv_work(B, H, Tmax, r_k, 16, dev)
+    out = torch.empty((B, H, Tmax), dtype=torch.float32, device=dev)
+    with _on(dev):
+        L.check(lib.asvd_lowrank_kv_scores(q.data_ptr(), ck.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin), L.F16,
+                                           KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), out.data_ptr(),
+                                           work.data_ptr(), work.numel(), _stream(q)), "asvd_lowrank_kv_scores")
+    return out
+
+
+def lowrank_kv_decode(q, ck, cv, lens, Ak, Av, H_kv, scale, bk=None, bv=None, rope=None, work=None, out=None):
+    """out [B, H, D] fp16 = softmax over t < lens[b] of the scores above, times V_h = C_v A_v[kv(h)]^T + b_v, for ONE new query token per
+    sequence (K20, asvd_lowrank_kv_decode).  cv [B, Tmax, r_v] fp16 like ck, Av [H_kv * D, r_v] fp16.  A sequence with lens[b] == 0 gets
+    zeros.  Asynchronous on the current stream, no host sync, graph-capturable when `work` and `out` are given."""
+    B, H, D, r_k, Tmax, mode, cos, sin = _kv_args("lowrank_kv_decode", q, ck, lens, Ak, bk, rope, H_kv)
+    dev = q.device
+    r_v = _kv_cache_arg("lowrank_kv_decode", cv, B, dev)
+    if cv.shape[1] != Tmax:
+        raise ValueError("lowrank_kv_decode: ck and cv hold different token counts")
+    if Av.dtype != torch.float16 or tuple(Av.shape) != (H_kv * D, r_v) or not Av.is_contiguous() or Av.device != dev or Av.data_ptr() % 16:
+        raise ValueError(f"lowrank_kv_decode needs Av [H_kv * D, r_v] fp16 contiguous (got {tuple(Av.shape)} {Av.dtype})")
+    if bv is not None and (bv.dtype != torch.float16 or bv.numel() != H_kv * D or not bv.is_contiguous() or bv.device != dev):
+        raise ValueError("lowrank_kv_decode needs bv [H_kv * D] fp16 contiguous or None")
+    _dev(q, "q")
+    lib = L.load(True)
+    if work is None:
+        work = lowrank_kv_work(B, H, Tmax, r_k, r_v, dev)
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float16, device=dev)
+    elif out.dtype != torch.float16 or tuple(out.shape) != (B, H, D) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("lowrank_kv_decode: out must be [B, H, D] fp16 contiguous on the device of q")
+    with _on(dev):
+        L.check(lib.asvd_lowrank_kv_decode(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), lens.data_ptr(), Ak.data_ptr(), Av.data_ptr(), _ptr(bk),
+                                           _ptr(bv), _ptr(cos), _ptr(sin), L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, r_v, Tmax,
+                                           ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(),
+                                           _stream(q)), "asvd_lowrank_kv_decode")
+    return out
+
+
 PROFILE_CLASSES = ["pack", "sgram", "evd", "supdate", "finalize", "snapshot", "gram1", "update1", "supgram"]
 
 

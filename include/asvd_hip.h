@@ -566,6 +566,40 @@ int asvd_svd_get_pair_counts(long long* counts_host);
  * synchronises once per sweep).  Fills at most `cap` entries; returns the number of sweeps. */
 int asvd_svd_get_sweep_times(float* ms_host, long long* rotated_host, int cap);
 
+/* ---------------------------------------------------------------------------------------------
+ * K20: one decode step of attention on a LOW-RANK KV cache (csrc/lowrank_kv.hip, DESIGN.md 4 "K20").
+ * For a model whose k_proj / v_proj are SVDLinear(BLinear: hidden -> r, ALinear: r -> H_kv * D) the cache holds the BLinear outputs
+ * ck [B, Tmax, r_k] and cv [B, Tmax, r_v] (fp16; row and batch strides in ELEMENTS, multiples of 8, 16-byte aligned bases) instead of K and V.
+ * Ak [H_kv * D, r_k] and Av [H_kv * D, r_v] are the ALinear weights (fp16, contiguous), bk / bv their biases [H_kv * D] or NULL,
+ * q [B, H, D] the query of the new token (already rotated in mode HALF), lens int32 [B] on the device with 0 <= lens[b] <= Tmax
+ * (values outside are clamped), head h reads KV head h / (H / H_kv).  Replaces, for one new token, the reference's
+ *     k = k_proj(x); v = v_proj(x); cat with the cached K, V; softmax(q k^T * scale) v        (K and V cached in full)
+ * rope_mode ASVD_KV_ROPE_NONE: the scores use q~ = fp16(A_k^T q); bk adds one constant per head, drops out of the softmax and is ignored.
+ * rope_mode ASVD_KV_ROPE_HALF: K is rebuilt tile by tile and rotated with rows of cos_tab / sin_tab (fp32 [Tmax, D/2], 16-byte aligned, row t
+ *   for cache position t, pairs (i, i + D/2) as in HF rotate_half); bk must be NULL.
+ * Served: dtype ASVD_F16 only, D 64 or 128, any H >= 1, H_kv dividing H, r_k and r_v multiples of 16 up to 16384, B >= 1.  Anything else,
+ * a NULL or misaligned pointer or stride included, is ASVD_E_BADARG before any device call.  A sequence with lens[b] == 0 gets a zero row.
+ * Nothing at cache positions >= lens[b] reaches an output; a non-finite value stays in its own sequence; results do not depend on timing.
+ * All entries are asynchronous on `stream` (plain launches, graph-capturable); work is the caller's, 16-byte aligned.
+ *   asvd_lowrank_kv_plan      host only: the token tile of the score kernels and the split length / count of the softmax-weighted sum for
+ *                             (B, H, Tmax); the count is a function of these and of the 256 compute units of gfx950 parts alone.
+ *   asvd_lowrank_kv_worksize  host only: bytes of `work` = q~ fp16 [B, Hpad, r_k] + scores fp32 [B, H, Tld] + (max, sum) and partial
+ *                             sums fp32 [B, splits, Hpad, 2 + r_v], each rounded up to 256 bytes; Hpad = H up to 32, Tld = Tmax up to 16.
+ *   asvd_lowrank_kv_scores    S[b, h, t] = scale * q_h . K_h[t] for t < lens[b] into the workspace and, if scores_out is not NULL,
+ *                             to scores_out fp32 [B, H, Tmax] (zeros at t >= lens[b]).  Needs the first two parts of the workspace only.
+ *   asvd_lowrank_kv_decode    all stages; out [B, H, D] fp16. */
+#define ASVD_KV_ROPE_NONE 0
+#define ASVD_KV_ROPE_HALF 1
+int asvd_lowrank_kv_plan(int64_t B, int64_t H, int64_t Tmax, int64_t* token_tile, int64_t* split_len, int64_t* n_splits);
+int asvd_lowrank_kv_worksize(int64_t B, int64_t H, int64_t Tmax, int64_t r_k, int64_t r_v, size_t* bytes);
+int asvd_lowrank_kv_scores(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cos_tab, const void* sin_tab,
+                           int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax,
+                           int64_t ck_row_stride, int64_t ck_batch_stride, void* scores_out, void* work, size_t work_bytes, void* stream);
+int asvd_lowrank_kv_decode(const void* q, const void* ck, const void* cv, const void* lens, const void* Ak, const void* Av, const void* bk,
+                           const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
+                           int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
+                           int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
