@@ -76,19 +76,31 @@ def run_weight_quant(model, args):
 def run_kv_cache_decode(model, calib_loader, args):
     """--kv_cache_decode_tokens N: what the compressed k_proj / v_proj buy at run time.  Prints the bytes one token occupies in the ordinary
     and in the low-rank KV cache (all layers), then greedy-decodes N tokens from the first calibration sample on both caches (K20 on the low-rank
-    one, asvd4llm_amd/kv_cache.py) and prints the largest difference of their logits."""
+    one, asvd4llm_amd/kv_cache.py) and prints the largest difference of their logits.  --kv_cache_quant int8 adds the int8 form of the low-rank
+    cache (K21): its bytes per token, and the same forced token stream decoded on it."""
     from asvd4llm_amd.kv_cache import greedy_decode, is_llama_family, kv_ranks
+    from asvd4llm_amd.ops import lowrank_kv_groups
     dense = 0
-    ranks = {}
+    ranks, pairs = {}, {}
     for name, m in model.named_modules():
         if name.endswith(("k_proj", "v_proj")):
             width = m.ALinear.out_features if hasattr(m, "ALinear") else m.out_features
             dense += 2 * width
             ranks.setdefault(name.rsplit(".", 1)[0], []).append(m.BLinear.out_features if hasattr(m, "BLinear") else width)
+            pairs.setdefault(name.rsplit(".", 1)[0], []).append(hasattr(m, "BLinear") and hasattr(m, "ALinear"))
+    pairs = [all(v) for v in pairs.values()]   # a layer is cached low-rank (and quantised) where k_proj and v_proj are both factor pairs
     ranks = kv_ranks(model) if is_llama_family(model) else [tuple(v) for v in ranks.values()]   # the runner's cache: what is realised
     low = 2 * sum(sum(r) for r in ranks)
     print(f"kv cache ranks (k, v) per layer: {ranks}")
     print(f"kv cache bytes per token: dense {dense}, low-rank {low} (ratio {low / max(dense, 1):.4f})")
+    int8 = getattr(args, "kv_cache_quant", "none") == "int8"
+    if int8 and any(p and (r[0] % 16 or r[1] % 16) for p, r in zip(pairs, ranks)):
+        print("kv cache int8: the format needs ranks that are multiples of 16 (--rank_align 16); skipped")
+        int8 = False
+    if int8:   # a byte per code and an fp32 scale per 32 columns where the layer is low-rank, fp16 K and V elsewhere
+        low8 = sum(sum(w + 4 * lowrank_kv_groups(w) for w in r) if p else 2 * sum(r) for p, r in zip(pairs, ranks))
+        print(f"kv cache bytes per token: int8 low-rank {low8} (ratio {low8 / max(dense, 1):.4f} of dense, {low8 / max(low, 1):.4f} of low-rank); "
+              f"int8 layers: {[i for i, p in enumerate(pairs) if p]}")
     if not is_llama_family(model):
         print("kv cache decode: the greedy runner serves Llama-family models only; this model is served at the LowRankKVAttention level")
         return
@@ -99,6 +111,11 @@ def run_kv_cache_decode(model, calib_loader, args):
     diff = (logits_low.float() - logits_dense.float()).abs().max().item()
     print(f"kv cache decode: {n} tokens, largest logit difference {diff:.4e} (largest logit {logits_dense.float().abs().max().item():.4e}), "
           f"tokens equal: {bool((toks_low == toks_dense).all())}")
+    if int8:
+        toks_q8, logits_q8 = greedy_decode(model, ids, n, cache="lowrank", forced=toks_low, kv_quant="int8")
+        diff8 = (logits_q8.float() - logits_dense.float()).abs().max().item()
+        print(f"kv cache decode, int8 low-rank cache: {n} tokens, largest logit difference {diff8:.4e} against the dense cache "
+              f"(fp16 low-rank cache: {diff:.4e}), tokens equal: {bool((toks_q8 == toks_dense).all())}")
 
 
 def main(args):
@@ -223,6 +240,9 @@ def build_parser():
                         help="after the compression print the bytes per token of the ordinary and of the low-rank KV cache (k_proj / v_proj kept as "
                              "their r-wide BLinear outputs) and greedy-decode this many tokens on both (Llama-family models; the low-rank cache runs "
                              "the K20 decode-attention kernel where it serves the shape).  0 (default): nothing happens")
+    parser.add_argument("--kv_cache_quant", choices=["none", "int8"], default="none",
+                        help="read by the --kv_cache_decode_tokens report only.  int8: also print the bytes per token of the int8 low-rank cache (K21: "
+                             "8-bit codes and one fp32 scale per token and 32 latent columns) and decode the same token stream on it")
     parser.add_argument("--exclude_lm_head", action="store_true", help="do not hook/sweep/compress lm_head (the reference includes it)")
     parser.add_argument("--save_repo", type=str, default="", help="write the compressed model in the exported HF-repo layout of the reference (truncation_ranks in config.json)")
     parser.add_argument("--no_fused_sweep", dest="fused_sweep", action="store_false",

@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["svd_jacobi.hip", "evd_wave.hip", "aux_kernels.hip", "sigma_max.hip", "comm.hip", "lowrank_forward.hip", "rtn_quant.hip", "w8_linear.hip", "reorth.hip", "lowrank_kv.hip"]
+SOURCES = ["svd_jacobi.hip", "evd_wave.hip", "aux_kernels.hip", "sigma_max.hip", "comm.hip", "lowrank_forward.hip", "rtn_quant.hip", "w8_linear.hip", "reorth.hip", "lowrank_kv.hip", "lowrank_kv_q8.hip"]
 LIB = os.path.join(HERE, "libasvd_hip.so")
 
 

@@ -22,7 +22,14 @@
 // masked TOKEN is a reduction index (stage c) its p is set to 0 by a select and its cache value is replaced by 0, never multiplied.
 // Nothing at positions >= len[b] of a cache, the unwritten tail of S included, can reach an output; a non-finite value in one
 // sequence's cache or query stays in that sequence (no reduction crosses b).  Two calls give the same bits: no order depends on timing.
-#include "common.h"
+//
+// K21: the cache may hold int8 codes and one fp32 scale per token and 32 rank columns instead (the format of lowrank_kv_q8.h).  Stages b and c
+// are templated on that; the two forms differ ONLY in how a lane obtains its cache operand (KvTok, KvCol below): the int8 form loads 8 codes
+// (stage b: 8 columns of one token, one 8-byte load and one scale; stage c: 8 tokens of one column, a byte and a scale each) and
+// dequantises them in registers, d = fp16(float(code) * s).  The fp16 values then feed the same MFMA in the same order, so an int8 call
+// returns the bits of the fp16 call on the dequantised cache.  Masked tokens load code AND scale from the clamped address and are replaced
+// by 0 with the same select.  Stages a and d, the plan and the workspace do not depend on the cache format.
+#include "lowrank_kv_q8.h"
 
 namespace {
 
@@ -78,22 +85,59 @@ __global__ __launch_bounds__(256) void kv_qtilde_kernel(const uint16_t* __restri
     qt[((int64_t)b * hpad + h) * r_k + j] = f32_to_f16_bits(acc);
 }
 
+// ---- how a lane obtains its cache operand: Q8 = false reads fp16 values, Q8 = true int8 codes and their group scales (K21) -------------
+// stage b: the 8 rank columns 16 k + 8 g .. + 7 of token t; they lie in ONE 32-column group, k >> 1
+template <bool Q8> struct KvTok;
+template <> struct KvTok<false> {
+    const uint4* p;
+    __device__ __forceinline__ KvTok(const void* c, int64_t rs, int64_t bs, const float*, int64_t, int64_t, int b, int t, int g)
+        : p((const uint4*)((const uint16_t*)c + (int64_t)b * bs + (int64_t)t * rs + 8 * g)) {}
+    __device__ __forceinline__ f16x8 operator()(int k) const { return __builtin_bit_cast(f16x8, p[2 * k]); }
+};
+template <> struct KvTok<true> {
+    const uint2* p;
+    const float* s;
+    __device__ __forceinline__ KvTok(const void* c, int64_t rs, int64_t bs, const float* sc, int64_t srs, int64_t sbs, int b, int t, int g)
+        : p((const uint2*)((const int8_t*)c + (int64_t)b * bs + (int64_t)t * rs + 8 * g)), s(sc + (int64_t)b * sbs + (int64_t)t * srs) {}
+    __device__ __forceinline__ f16x8 operator()(int k) const { return kv_q8_dequant8(p[2 * k], s[k >> 1]); }
+};
+// stage c: rank column j of any token t (the bits of the fp16 value)
+template <bool Q8> struct KvCol;
+template <> struct KvCol<false> {
+    const uint16_t* p;
+    int64_t rs;
+    __device__ __forceinline__ KvCol(const void* c, int64_t rs_, int64_t bs, const float*, int64_t, int64_t, int b, int j)
+        : p((const uint16_t*)c + (int64_t)b * bs + j), rs(rs_) {}
+    __device__ __forceinline__ uint16_t operator()(int t) const { return p[(int64_t)t * rs]; }
+};
+template <> struct KvCol<true> {
+    const int8_t* p;
+    const float* s;
+    int64_t rs, srs;
+    __device__ __forceinline__ KvCol(const void* c, int64_t rs_, int64_t bs, const float* sc, int64_t srs_, int64_t sbs, int b, int j)
+        : p((const int8_t*)c + (int64_t)b * bs + j), s(sc + (int64_t)b * sbs + j / KV_Q8_GROUP), rs(rs_), srs(srs_) {}
+    __device__ __forceinline__ uint16_t operator()(int t) const {
+        return __builtin_bit_cast(uint16_t, kv_q8_dequant((int)p[(int64_t)t * rs], s[(int64_t)t * srs]));
+    }
+};
+
 // ---- b, no rotation: S = scale * q~ C_k^T, heads in the accumulator registers, tokens on the lanes (coalesced stores) -----------------
-__global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __restrict__ qt, const uint16_t* __restrict__ ck, int64_t rs, int64_t bs,
-                                                             const int* __restrict__ lens, float* __restrict__ S, float scale, int H, int r_k,
-                                                             int Tmax, int hpad, int tld) {
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __restrict__ qt, const void* __restrict__ ck, int64_t rs, int64_t bs,
+                                                             const float* __restrict__ sk, int64_t srs, int64_t sbs, const int* __restrict__ lens,
+                                                             float* __restrict__ S, float scale, int H, int r_k, int Tmax, int hpad, int tld) {
     const int b = blockIdx.x, len = kv_len(lens, b, Tmax);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 31, g = lane >> 5;
     const int t0 = blockIdx.y * KV_TOK_TILE + wave * 32, h0 = blockIdx.z * 32;
     if (t0 >= len) return;
     const uint4* qp = (const uint4*)(qt + ((int64_t)b * hpad + min(h0 + i, H - 1)) * r_k + 8 * g);
-    const uint4* cp = (const uint4*)(ck + (int64_t)b * bs + (int64_t)min(t0 + i, len - 1) * rs + 8 * g);
+    const KvTok<Q8> cp(ck, rs, bs, sk, srs, sbs, b, min(t0 + i, len - 1), g);
     f32x16 acc;
 #pragma unroll
     for (int x = 0; x < 16; ++x) acc[x] = 0.f;
     const int nk = r_k / 16;
     for (int k = 0; k < nk; ++k)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, qp[2 * k]), __builtin_bit_cast(f16x8, cp[2 * k]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, qp[2 * k]), cp(k), acc, 0, 0, 0);
     const int t = t0 + i;
     if (t < len) {
 #pragma unroll
@@ -108,8 +152,9 @@ __global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __r
 // Feature d of the tile sits in register x of accumulator n with d = 32 n + acc_row(x, g), so the partner d + D/2 of the rotation is
 // register x of accumulator n + D/64 of the SAME lane: the rotation needs no lane movement, the dot over d is a sum over registers plus
 // one exchange between the two lane halves.  All heads of a KV group reuse the rotated tile.
-template <int D>
-__global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ ck, int64_t rs, int64_t bs,
+template <int D, bool Q8>
+__global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __restrict__ q, const void* __restrict__ ck, int64_t rs, int64_t bs,
+                                                             const float* __restrict__ sk, int64_t srs, int64_t sbs,
                                                              const int* __restrict__ lens, const uint16_t* __restrict__ Ak,
                                                              const float* __restrict__ cs, const float* __restrict__ sn, float* __restrict__ S,
                                                              float scale, int H, int group, int r_k, int Tmax, int tld) {
@@ -119,7 +164,7 @@ __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __r
     const int t0 = blockIdx.y * KV_TOK_TILE + wave * 32;
     if (t0 >= len) return;
     const int tc = min(t0 + i, len - 1);   // masked lanes work on a valid token and store nothing
-    const uint4* cp = (const uint4*)(ck + (int64_t)b * bs + (int64_t)tc * rs + 8 * g);
+    const KvTok<Q8> cp(ck, rs, bs, sk, srs, sbs, b, tc, g);
     const uint4* ap = (const uint4*)(Ak + ((int64_t)kvh * D + i) * r_k + 8 * g);
     const int64_t astep = (int64_t)32 * r_k / 8;   // 32 feature rows, in uint4
     f32x16 acc[NT];
@@ -129,7 +174,7 @@ __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __r
         for (int x = 0; x < 16; ++x) acc[n][x] = 0.f;
     const int nk = r_k / 16;
     for (int k = 0; k < nk; ++k) {
-        const f16x8 c = __builtin_bit_cast(f16x8, cp[2 * k]);
+        const f16x8 c = cp(k);
 #pragma unroll
         for (int n = 0; n < NT; ++n)
             acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ap[n * astep + 2 * k]), c, acc[n], 0, 0, 0);
@@ -180,8 +225,9 @@ __global__ __launch_bounds__(256) void kv_scores_copy_kernel(const float* __rest
 }
 
 // ---- c: one split of the tokens.  m, l and O~[32 heads, 32 ranks per wave] = p C_v ------------------------------------------------------
-__global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S, const uint16_t* __restrict__ cv, int64_t rs, int64_t bs,
-                                                    const int* __restrict__ lens, float* __restrict__ ml, float* __restrict__ Op, int H, int r_v,
+template <bool Q8>
+__global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S, const void* __restrict__ cv, int64_t rs, int64_t bs,
+                                                    const float* __restrict__ sv, int64_t srs, int64_t sbs, const int* __restrict__ lens, float* __restrict__ ml, float* __restrict__ Op, int H, int r_v,
                                                     int Tmax, int hpad, int tld, int L, int ns) {
     const int nhb = hpad / 32;
     const int b = blockIdx.x / nhb, h0 = (blockIdx.x % nhb) * 32, s = blockIdx.y, len = kv_len(lens, b, Tmax);
@@ -204,7 +250,7 @@ __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S,
     }
     m = fmaxf(m, __shfl_xor(m, 32, 64));
     // pass 2: p = fp16(exp(S - m)) is the A operand (row = head i, k = token), C_v the B operand (k = token, column = rank j0 + i)
-    const uint16_t* vcol = cv + (int64_t)b * bs + min(j0 + i, r_v - 1);
+    const KvCol<Q8> vcol(cv, rs, bs, sv, srs, sbs, b, min(j0 + i, r_v - 1));
     f32x16 acc;
 #pragma unroll
     for (int x = 0; x < 16; ++x) acc[x] = 0.f;
@@ -220,7 +266,7 @@ __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S,
             const _Float16 p = live ? (_Float16)expf(v[u] - m) : (_Float16)0.f;
             l += (float)p;
             pf[u] = p;
-            const uint16_t c = vcol[(int64_t)min(tt + u, end - 1) * rs];
+            const uint16_t c = vcol(min(tt + u, end - 1));
             vf[u] = __builtin_bit_cast(_Float16, (uint16_t)(live ? c : (uint16_t)0));
         }
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(pf, vf, acc, 0, 0, 0);
@@ -305,14 +351,14 @@ inline bool mis16(const void* p) { return ((uintptr_t)p & 15) != 0; }
 // the argument rules shared by both entries; nothing here touches the device
 int kv_check_common(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cs, const void* sn, int dtype,
                     int rope_mode, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax, int64_t ck_rs, int64_t ck_bs,
-                    const void* work) {
+                    const void* work, int64_t unit = 8) {   // unit: cache elements in 16 bytes (8 fp16 values, 16 int8 codes)
     if (!q || !ck || !lens || !Ak || !work) return ASVD_E_BADARG;
     if (dtype != ASVD_F16) return ASVD_E_BADARG;
     if (rope_mode != ASVD_KV_ROPE_NONE && rope_mode != ASVD_KV_ROPE_HALF) return ASVD_E_BADARG;
     if (D != 64 && D != 128) return ASVD_E_BADARG;
     if (B < 1 || B > (1 << 20) || H < 1 || H > 4096 || H_kv < 1 || H % H_kv || Tmax < 1 || Tmax > (1 << 22)) return ASVD_E_BADARG;
     if (r_k < 16 || r_k % 16 || r_k > KV_MAX_RANK) return ASVD_E_BADARG;
-    if (ck_rs < r_k || ck_rs % 8 || ck_bs % 8 || ck_bs < 0 || (B > 1 && ck_bs < Tmax * ck_rs)) return ASVD_E_BADARG;
+    if (ck_rs < r_k || ck_rs % unit || ck_bs % unit || ck_bs < 0 || (B > 1 && ck_bs < Tmax * ck_rs)) return ASVD_E_BADARG;
     if (mis16(q) || mis16(ck) || mis16(Ak) || mis16(work) || ((uintptr_t)lens & 3)) return ASVD_E_BADARG;
     if (rope_mode == ASVD_KV_ROPE_HALF) {
         if (!cs || !sn || mis16(cs) || mis16(sn) || bk) return ASVD_E_BADARG;   // a key bias does not commute with the rotation's absorbed form
@@ -320,26 +366,96 @@ int kv_check_common(const void* q, const void* ck, const void* lens, const void*
     return ASVD_OK;
 }
 
+// the second cache of the whole op
+int kv_check_values(const void* cv, const void* Av, const void* out, int64_t B, int64_t r_v, int64_t Tmax, int64_t cv_rs, int64_t cv_bs, int64_t unit) {
+    if (!cv || !Av || !out || mis16(cv) || mis16(Av) || mis16(out)) return ASVD_E_BADARG;
+    if (r_v < 16 || r_v % 16 || r_v > KV_MAX_RANK) return ASVD_E_BADARG;
+    if (cv_rs < r_v || cv_rs % unit || cv_bs % unit || cv_bs < 0 || (B > 1 && cv_bs < Tmax * cv_rs)) return ASVD_E_BADARG;
+    return ASVD_OK;
+}
+
+// the scales of an int8 cache: fp32 [B, Tmax, >= ceil(r / 32)], strides in floats
+int kv_check_scales(const void* s, int64_t B, int64_t r, int64_t Tmax, int64_t s_rs, int64_t s_bs) {
+    if (!s || ((uintptr_t)s & 3)) return ASVD_E_BADARG;
+    if (s_rs < kv_q8_groups(r) || s_bs < 0 || (B > 1 && s_bs < Tmax * s_rs)) return ASVD_E_BADARG;
+    return ASVD_OK;
+}
+
+template <bool Q8>
 int kv_scores_launch(const KvPlan& p, const void* q, const void* ck, const void* lens, const void* Ak, const void* cs, const void* sn, int rope_mode,
-                     float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax, int64_t ck_rs, int64_t ck_bs, void* work,
-                     hipStream_t st) {
+                     float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax, int64_t ck_rs, int64_t ck_bs, const float* sk,
+                     int64_t sk_rs, int64_t sk_bs, void* work, hipStream_t st) {
     uint16_t* qt = (uint16_t*)((char*)work + p.off_qt);
     float* S = (float*)((char*)work + p.off_s);
     const int group = (int)(H / H_kv), ntile = (int)ceil_div64(Tmax, KV_TOK_TILE);
     if (rope_mode == ASVD_KV_ROPE_NONE) {
         hipLaunchKernelGGL(kv_qtilde_kernel, dim3((unsigned)(B * H), (unsigned)ceil_div64(r_k, 256)), dim3(256), 0, st, (const uint16_t*)q,
                            (const uint16_t*)Ak, qt, (int)H, group, (int)D, (int)r_k, (int)p.hpad);
-        hipLaunchKernelGGL(kv_scores_none_kernel, dim3((unsigned)B, ntile, (unsigned)(p.hpad / 32)), dim3(256), 0, st, (const uint16_t*)qt,
-                           (const uint16_t*)ck, ck_rs, ck_bs, (const int*)lens, S, scale, (int)H, (int)r_k, (int)Tmax, (int)p.hpad, (int)p.tld);
+        hipLaunchKernelGGL((kv_scores_none_kernel<Q8>), dim3((unsigned)B, ntile, (unsigned)(p.hpad / 32)), dim3(256), 0, st, (const uint16_t*)qt,
+                           ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, S, scale, (int)H, (int)r_k, (int)Tmax, (int)p.hpad, (int)p.tld);
     } else if (D == 64) {
-        hipLaunchKernelGGL(kv_scores_half_kernel<64>, dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
-                           (const uint16_t*)ck, ck_rs, ck_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
+        hipLaunchKernelGGL((kv_scores_half_kernel<64, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
+                           ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
                            (int)H, group, (int)r_k, (int)Tmax, (int)p.tld);
     } else {
-        hipLaunchKernelGGL(kv_scores_half_kernel<128>, dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
-                           (const uint16_t*)ck, ck_rs, ck_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
+        hipLaunchKernelGGL((kv_scores_half_kernel<128, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
+                           ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
                            (int)H, group, (int)r_k, (int)Tmax, (int)p.tld);
     }
+    ASVD_HIP_CHECK(hipGetLastError());
+    return ASVD_OK;
+}
+
+template <bool Q8>
+int kv_scores_entry(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                    const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax,
+                    int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride, void* scores_out, void* work,
+                    size_t work_bytes, void* stream) {
+    int rc = kv_check_common(q, ck, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride, work,
+                             Q8 ? 16 : 8);
+    if (rc == ASVD_OK && Q8) rc = kv_check_scales(sk, B, r_k, Tmax, sk_row_stride, sk_batch_stride);
+    if (rc != ASVD_OK) return rc;
+    if (scores_out && ((uintptr_t)scores_out & 3)) return ASVD_E_BADARG;
+    const KvPlan p = kv_plan(B, H, Tmax, r_k, 16);
+    if (work_bytes < p.off_ml) return ASVD_E_WORKSPACE;   // q~ and S only
+    const int lrc = kv_scores_launch<Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                         ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, (hipStream_t)stream);
+    if (lrc != ASVD_OK) return lrc;
+    if (scores_out) {
+        hipLaunchKernelGGL(kv_scores_copy_kernel, dim3((unsigned)(B * H), (unsigned)ceil_div64(Tmax, 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const float*)((char*)work + p.off_s), (const int*)lens, (float*)scores_out, (int)H, (int)Tmax, (int)p.tld);
+        ASVD_HIP_CHECK(hipGetLastError());
+    }
+    return ASVD_OK;
+}
+
+template <bool Q8>
+int kv_decode_entry(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak, const void* Av,
+                    const void* bk, const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
+                    int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
+                    int64_t cv_row_stride, int64_t cv_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride, int64_t sv_row_stride,
+                    int64_t sv_batch_stride, void* out, void* work, size_t work_bytes, void* stream) {
+    const int64_t unit = Q8 ? 16 : 8;
+    int rc = kv_check_common(q, ck, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride, work, unit);
+    if (rc == ASVD_OK) rc = kv_check_values(cv, Av, out, B, r_v, Tmax, cv_row_stride, cv_batch_stride, unit);
+    if (rc == ASVD_OK && Q8) rc = kv_check_scales(sk, B, r_k, Tmax, sk_row_stride, sk_batch_stride);
+    if (rc == ASVD_OK && Q8) rc = kv_check_scales(sv, B, r_v, Tmax, sv_row_stride, sv_batch_stride);
+    if (rc != ASVD_OK) return rc;
+    const KvPlan p = kv_plan(B, H, Tmax, r_k, r_v);
+    if (work_bytes < p.total) return ASVD_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int lrc = kv_scores_launch<Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                         ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, st);
+    if (lrc != ASVD_OK) return lrc;
+    const float* S = (const float*)((char*)work + p.off_s);
+    float* ml = (float*)((char*)work + p.off_ml);
+    float* Op = (float*)((char*)work + p.off_o);
+    hipLaunchKernelGGL((kv_pv_kernel<Q8>), dim3((unsigned)(B * (p.hpad / 32)), (unsigned)p.n_splits, (unsigned)ceil_div64(r_v, 128)), dim3(256), 0, st, S,
+                       cv, cv_row_stride, cv_batch_stride, (const float*)sv, sv_row_stride, sv_batch_stride, (const int*)lens, ml, Op, (int)H, (int)r_v,
+                       (int)Tmax, (int)p.hpad, (int)p.tld, (int)p.split_len, (int)p.n_splits);
+    hipLaunchKernelGGL(kv_combine_kernel, dim3((unsigned)(B * H)), dim3(256), (size_t)r_v * sizeof(float), st, (const float*)ml, (const float*)Op,
+                       (const int*)lens, (const uint16_t*)Av, (const uint16_t*)bv, (uint16_t*)out, (int)H, (int)(H / H_kv), (int)D, (int)r_v,
+                       (int)Tmax, (int)p.hpad, (int)p.split_len, (int)p.n_splits);
     ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
 }
@@ -366,49 +482,36 @@ int asvd_lowrank_kv_worksize(int64_t B, int64_t H, int64_t Tmax, int64_t r_k, in
 int asvd_lowrank_kv_scores(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cos_tab, const void* sin_tab,
                            int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax,
                            int64_t ck_row_stride, int64_t ck_batch_stride, void* scores_out, void* work, size_t work_bytes, void* stream) {
-    const int rc = kv_check_common(q, ck, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride, work);
-    if (rc != ASVD_OK) return rc;
-    if (scores_out && ((uintptr_t)scores_out & 3)) return ASVD_E_BADARG;
-    const KvPlan p = kv_plan(B, H, Tmax, r_k, 16);
-    if (work_bytes < p.off_ml) return ASVD_E_WORKSPACE;   // q~ and S only
-    const int lrc = kv_scores_launch(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride,
-                                     work, (hipStream_t)stream);
-    if (lrc != ASVD_OK) return lrc;
-    if (scores_out) {
-        hipLaunchKernelGGL(kv_scores_copy_kernel, dim3((unsigned)(B * H), (unsigned)ceil_div64(Tmax, 256)), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)((char*)work + p.off_s), (const int*)lens, (float*)scores_out, (int)H, (int)Tmax, (int)p.tld);
-        ASVD_HIP_CHECK(hipGetLastError());
-    }
-    return ASVD_OK;
+    return kv_scores_entry<false>(q, ck, nullptr, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                  ck_batch_stride, 0, 0, scores_out, work, work_bytes, stream);
 }
 
 int asvd_lowrank_kv_decode(const void* q, const void* ck, const void* cv, const void* lens, const void* Ak, const void* Av, const void* bk,
                            const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
                            int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
                            int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream) {
-    const int rc = kv_check_common(q, ck, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride, work);
-    if (rc != ASVD_OK) return rc;
-    if (!cv || !Av || !out || mis16(cv) || mis16(Av) || mis16(out)) return ASVD_E_BADARG;
-    if (r_v < 16 || r_v % 16 || r_v > KV_MAX_RANK) return ASVD_E_BADARG;
-    if (cv_row_stride < r_v || cv_row_stride % 8 || cv_batch_stride % 8 || cv_batch_stride < 0 || (B > 1 && cv_batch_stride < Tmax * cv_row_stride))
-        return ASVD_E_BADARG;
-    const KvPlan p = kv_plan(B, H, Tmax, r_k, r_v);
-    if (work_bytes < p.total) return ASVD_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int lrc = kv_scores_launch(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride, ck_batch_stride,
-                                     work, st);
-    if (lrc != ASVD_OK) return lrc;
-    const float* S = (const float*)((char*)work + p.off_s);
-    float* ml = (float*)((char*)work + p.off_ml);
-    float* Op = (float*)((char*)work + p.off_o);
-    hipLaunchKernelGGL(kv_pv_kernel, dim3((unsigned)(B * (p.hpad / 32)), (unsigned)p.n_splits, (unsigned)ceil_div64(r_v, 128)), dim3(256), 0, st, S,
-                       (const uint16_t*)cv, cv_row_stride, cv_batch_stride, (const int*)lens, ml, Op, (int)H, (int)r_v, (int)Tmax, (int)p.hpad,
-                       (int)p.tld, (int)p.split_len, (int)p.n_splits);
-    hipLaunchKernelGGL(kv_combine_kernel, dim3((unsigned)(B * H)), dim3(256), (size_t)r_v * sizeof(float), st, (const float*)ml, (const float*)Op,
-                       (const int*)lens, (const uint16_t*)Av, (const uint16_t*)bv, (uint16_t*)out, (int)H, (int)(H / H_kv), (int)D, (int)r_v,
-                       (int)Tmax, (int)p.hpad, (int)p.split_len, (int)p.n_splits);
-    ASVD_HIP_CHECK(hipGetLastError());
-    return ASVD_OK;
+    return kv_decode_entry<false>(q, ck, cv, nullptr, nullptr, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v,
+                                  Tmax, ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, 0, 0, 0, 0, out, work, work_bytes, stream);
+}
+
+// K21: the same stages on an int8 cache; ck / cv are codes (strides in bytes), sk / sv their fp32 group scales (strides in floats)
+int asvd_lowrank_kv_scores_q8(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                              const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k,
+                              int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride,
+                              void* scores_out, void* work, size_t work_bytes, void* stream) {
+    return kv_scores_entry<true>(q, ck, sk, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                 ck_batch_stride, sk_row_stride, sk_batch_stride, scores_out, work, work_bytes, stream);
+}
+
+int asvd_lowrank_kv_decode_q8(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
+                              const void* Av, const void* bk, const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode,
+                              float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax,
+                              int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride, int64_t cv_batch_stride, int64_t sk_row_stride,
+                              int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work, size_t work_bytes,
+                              void* stream) {
+    return kv_decode_entry<true>(q, ck, cv, sk, sv, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
+                                 ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride, sv_row_stride,
+                                 sv_batch_stride, out, work, work_bytes, stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@ After the search, k_proj / v_proj are SVDLinear(BLinear: hidden -> r, ALinear: r
 outputs (r_k + r_v values per token and layer) instead of K and V (2 * H_kv * D values); ALinear moves to the other side of the attention
 product (csrc/lowrank_kv.hip, K20; DESIGN.md 4 "K20").
 
-  LowRankKVCache      preallocated C_k / C_v buffers per layer and the lengths, host and device side
+  LowRankKVCache      preallocated C_k / C_v buffers per layer and the lengths, host and device side; quant="int8" keeps a layer as 8-bit
+                      codes and one fp32 scale per token and 32 columns (K21, csrc/lowrank_kv_q8.hip; DESIGN.md 4 "K21")
   LowRankKVAttention  prefill / decode of one attention layer on that cache; decode runs K20, or torch on the same cache on a refusal
   greedy_decode       a runner for Llama-family HF models that owns its loop (no transformers attention or cache class is patched)
 """
@@ -29,9 +30,10 @@ class FactorPair(nn.Module):
 
 class _TokenCache:
     """[B, Tmax, width] buffers per layer, filled from the front; lengths per layer and sequence on the host (bookkeeping, no sync) and on
-    the device (int32, what the kernel reads)"""
+    the device (int32, what the kernel reads).  quant: None, "int8", or one of the two per layer.  An int8 layer holds ck / cv as int8 codes and
+    sk / sv as their fp32 group scales [B, Tmax, ceil(width / 32)] (sk / sv are None for the other layers); dtype then is the type read() answers in."""
 
-    def __init__(self, n_layers, batch, max_tokens, widths, device, dtype=torch.float16):
+    def __init__(self, n_layers, batch, max_tokens, widths, device, dtype=torch.float16, quant=None):
         if n_layers < 1 or batch < 1 or max_tokens < 1:
             raise ValueError("cache needs n_layers, batch, max_tokens >= 1")
         if isinstance(widths[0], int):
@@ -40,14 +42,52 @@ class _TokenCache:
             raise ValueError("one (key width, value width) pair for the cache, or one per layer")
         self.n_layers, self.batch, self.max_tokens, self.widths = n_layers, batch, max_tokens, [tuple(int(x) for x in w) for w in widths]
         self.device, self.dtype = torch.device(device), dtype
-        self.ck = [torch.empty(batch, max_tokens, w[0], dtype=dtype, device=self.device) for w in self.widths]
-        self.cv = [torch.empty(batch, max_tokens, w[1], dtype=dtype, device=self.device) for w in self.widths]
+        quant = [quant] * n_layers if quant is None or isinstance(quant, str) else list(quant)
+        if len(quant) != n_layers or any(q not in (None, "int8") for q in quant):
+            raise ValueError('quant is None, "int8", or a list with one of the two per layer')
+        if any(q and (w[0] % 16 or w[1] % 16) for q, w in zip(quant, self.widths)):
+            raise ValueError("an int8 layer needs widths that are multiples of 16")
+        self.quant = quant
+        kinds = [torch.int8 if q else dtype for q in quant]
+        self.ck = [torch.empty(batch, max_tokens, w[0], dtype=k, device=self.device) for w, k in zip(self.widths, kinds)]
+        self.cv = [torch.empty(batch, max_tokens, w[1], dtype=k, device=self.device) for w, k in zip(self.widths, kinds)]
+        scales = lambda i: [torch.empty(batch, max_tokens, ops.lowrank_kv_groups(w[i]), dtype=torch.float32, device=self.device) if q else None
+                            for w, q in zip(self.widths, quant)]
+        self.sk, self.sv = scales(0), scales(1)
         self.lens = torch.zeros(n_layers, batch, dtype=torch.int32, device=self.device)
         self.host_lens = [[0] * batch for _ in range(n_layers)]
 
     def reset(self):
         self.lens.zero_()
         self.host_lens = [[0] * self.batch for _ in range(self.n_layers)]
+
+    def _store(self, layer, seqs, t0, c, ck_rows, cv_rows):
+        """rows [len(seqs), c, width] into positions t0 .. t0 + c of the sequences `seqs` (a slice).  An int8 layer quantises them: with the
+        kernel when they are fp16 on the device, with the same definition in torch otherwise (through .half())"""
+        if c == 0:
+            return
+        if not self.quant[layer]:
+            self.ck[layer][seqs, t0:t0 + c] = ck_rows
+            self.cv[layer][seqs, t0:t0 + c] = cv_rows
+            return
+        for codes, scales, rows in ((self.ck[layer], self.sk[layer], ck_rows), (self.cv[layer], self.sv[layer], cv_rows)):
+            if rows.is_cuda and rows.dtype == torch.float16:
+                if rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) % 8 or rows.data_ptr() % 16:
+                    rows = rows.contiguous()
+                ops.lowrank_kv_quant(rows, codes[seqs, t0:t0 + c], scales[seqs, t0:t0 + c])
+            else:
+                q, sc = ops.lowrank_kv_quant_torch(rows)
+                codes[seqs, t0:t0 + c] = q
+                scales[seqs, t0:t0 + c] = sc
+
+    def read(self, layer, T, dtype=None):
+        """(C_k, C_v) of the first T tokens of `layer` in `dtype` (default: the cache's): the values decode attends to, dequantised for an
+        int8 layer (fp16 values, K21's d = fp16(code * s)), a plain slice otherwise"""
+        dtype = dtype or self.dtype
+        if not self.quant[layer]:
+            return self.ck[layer][:, :T].to(dtype), self.cv[layer][:, :T].to(dtype)
+        return (ops.lowrank_kv_dequant(self.ck[layer][:, :T], self.sk[layer][:, :T]).to(dtype),
+                ops.lowrank_kv_dequant(self.cv[layer][:, :T], self.sv[layer][:, :T]).to(dtype))
 
     def append(self, layer, ck_new, cv_new, counts=None):
         """append ck_new / cv_new [B, n, width] to `layer`: a prefill chunk (n > 1) or one token.  counts: valid new tokens per sequence
@@ -66,13 +106,11 @@ class _TokenCache:
             raise IndexError(f"append: layer {layer} would pass max_tokens = {self.max_tokens} (lengths {before}, new {counts})")
         if len(set(before)) == 1 and len(set(counts)) == 1:
             t0, c = before[0], counts[0]
-            self.ck[layer][:, t0:t0 + c] = ck_new[:, :c]
-            self.cv[layer][:, t0:t0 + c] = cv_new[:, :c]
+            self._store(layer, slice(None), t0, c, ck_new[:, :c], cv_new[:, :c])
             self.lens[layer] += c
         else:
             for b in range(B):
-                self.ck[layer][b, before[b]:before[b] + counts[b]] = ck_new[b, :counts[b]]
-                self.cv[layer][b, before[b]:before[b] + counts[b]] = cv_new[b, :counts[b]]
+                self._store(layer, slice(b, b + 1), before[b], counts[b], ck_new[b:b + 1, :counts[b]], cv_new[b:b + 1, :counts[b]])
             self.lens[layer] += torch.tensor(counts, dtype=torch.int32).to(self.device)
         self.host_lens[layer] = [before[b] + counts[b] for b in range(B)]
         return before
@@ -81,7 +119,8 @@ class _TokenCache:
         """bytes one token occupies in this cache: in `layer`, or in all layers together"""
         size = torch.empty(0, dtype=self.dtype).element_size()
         layers = range(self.n_layers) if layer is None else [layer]
-        return sum(sum(self.widths[i]) * size for i in layers)
+        q8 = lambda w: w + 4 * ops.lowrank_kv_groups(w)   # a byte per code, an fp32 scale per 32 columns
+        return sum(sum(q8(w) for w in self.widths[i]) if self.quant[i] else sum(self.widths[i]) * size for i in layers)
 
     def dense_bytes_per_token(self, H_kv, D, layer=None):
         """bytes of the full K and V of one token: the cache this one replaces"""
@@ -90,8 +129,9 @@ class _TokenCache:
 
 
 class LowRankKVCache(_TokenCache):
-    """LowRankKVCache(n_layers, batch, max_tokens, ranks, device): ranks = (r_k, r_v), or one pair per layer.  ck[layer] / cv[layer] are the
-    BLinear outputs of k_proj / v_proj, [B, max_tokens, r] fp16; lens[layer] the int32 device lengths K20 reads."""
+    """LowRankKVCache(n_layers, batch, max_tokens, ranks, device, quant=None): ranks = (r_k, r_v), or one pair per layer.  ck[layer] / cv[layer]
+    are the BLinear outputs of k_proj / v_proj, [B, max_tokens, r] fp16; lens[layer] the int32 device lengths K20 reads.  quant="int8" (or a list
+    with None / "int8" per layer): ck / cv are int8 codes and sk / sv their fp32 scales (K21); append still takes fp16 rows, read() dequantises."""
 
 
 class DenseKVCache(_TokenCache):
@@ -156,8 +196,9 @@ class LowRankKVAttention(nn.Module):
         B, n = pos.shape
         T = max(cache.host_lens[layer])
         dt = q.dtype
-        K = self.k_proj.ALinear(cache.ck[layer][:, :T].to(dt)).view(B, T, self.n_kv_heads, self.head_dim)
-        V = self.v_proj.ALinear(cache.cv[layer][:, :T].to(dt)).view(B, T, self.n_kv_heads, self.head_dim)
+        ck, cv = cache.read(layer, T, dt)
+        K = self.k_proj.ALinear(ck).view(B, T, self.n_kv_heads, self.head_dim)
+        V = self.v_proj.ALinear(cv).view(B, T, self.n_kv_heads, self.head_dim)
         if self.rope is not None:
             cos, sin = self._rope_rows(torch.arange(T, device=q.device), torch.float32)
             K = rotate_half(K.float(), cos[None, :, None, :], sin[None, :, None, :]).to(dt)
@@ -213,10 +254,14 @@ class LowRankKVAttention(nn.Module):
         if work is None:
             work = self._work[key] = ops.lowrank_kv_work(B, self.n_heads, cache.max_tokens, r_k, r_v, hidden.device)
         kA, vA = self.k_proj.ALinear, self.v_proj.ALinear
-        o = ops.lowrank_kv_decode(q.reshape(B, self.n_heads, self.head_dim).contiguous(), cache.ck[layer], cache.cv[layer], cache.lens[layer],
-                                  kA.weight.detach(), vA.weight.detach(), self.n_kv_heads, self.scale,
-                                  bk=kA.bias.detach() if kA.bias is not None else None, bv=vA.bias.detach() if vA.bias is not None else None,
-                                  rope=self.rope, work=work)
+        q3 = q.reshape(B, self.n_heads, self.head_dim).contiguous()
+        kw = dict(bk=kA.bias.detach() if kA.bias is not None else None, bv=vA.bias.detach() if vA.bias is not None else None, rope=self.rope, work=work)
+        if cache.quant[layer]:   # K21: the same stages on codes and scales
+            o = ops.lowrank_kv_decode_q8(q3, cache.ck[layer], cache.cv[layer], cache.sk[layer], cache.sv[layer], cache.lens[layer],
+                                         kA.weight.detach(), vA.weight.detach(), self.n_kv_heads, self.scale, **kw)
+        else:
+            o = ops.lowrank_kv_decode(q3, cache.ck[layer], cache.cv[layer], cache.lens[layer], kA.weight.detach(), vA.weight.detach(),
+                                      self.n_kv_heads, self.scale, **kw)
         return self.o_proj(o.view(B, 1, self.n_heads * self.head_dim))
 
 
@@ -239,8 +284,9 @@ class _DenseAttention(nn.Module):
             q, k = rotate_half(q.float(), cos, sin).to(hidden.dtype), rotate_half(k.float(), cos, sin).to(hidden.dtype)
         cache.append(layer, k.reshape(B, n, -1).to(cache.dtype), self.v_proj(hidden).to(cache.dtype))
         T = max(cache.host_lens[layer])
-        K = cache.ck[layer][:, :T].to(hidden.dtype).view(B, T, self.n_kv_heads, self.head_dim).transpose(1, 2)
-        V = cache.cv[layer][:, :T].to(hidden.dtype).view(B, T, self.n_kv_heads, self.head_dim).transpose(1, 2)
+        K, V = cache.read(layer, T, hidden.dtype)
+        K = K.view(B, T, self.n_kv_heads, self.head_dim).transpose(1, 2)
+        V = V.view(B, T, self.n_kv_heads, self.head_dim).transpose(1, 2)
         rep = self.n_heads // self.n_kv_heads
         if rep > 1:
             K, V = K.repeat_interleave(rep, 1), V.repeat_interleave(rep, 1)
@@ -291,10 +337,12 @@ def kv_ranks(model):
 
 
 @torch.no_grad()
-def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=None):
+def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=None, kv_quant=None):
     """Greedy decoding of a Llama-family HF model with this module's caches: prefill input_ids [B, n], then one token per step.
     cache="lowrank": where k_proj / v_proj are factor pairs the cache holds their BLinear outputs and decode steps run K20 (kernel=True) or
     torch on the same cache (kernel=False, also on the CPU); a layer the search left uncompressed keeps its K and V.  cache="dense": the ordinary K / V cache, any k_proj / v_proj.
+    kv_quant="int8" (cache="lowrank" only): the layers whose k_proj and v_proj are both factor pairs keep their latents as int8 codes (K21) and
+    decode on them; an uncompressed layer keeps its fp16 K and V.
     forced [B, n_new] (optional): the tokens fed back instead of the runner's own choices, to compare runs on one token stream.
     Returns (tokens [B, n_new], logits [n_new, B, vocab]): logits[s] chose tokens[:, s]."""
     if not is_llama_family(model):
@@ -304,6 +352,8 @@ def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=
         raise ValueError('cache is "lowrank" or "dense"')
     if n_new < 1:
         raise ValueError("n_new >= 1")
+    if kv_quant not in (None, "int8") or (kv_quant and cache != "lowrank"):
+        raise ValueError('kv_quant is None or "int8", and only the low-rank cache is quantised')
     cfg = model.config
     H, H_kv = cfg.num_attention_heads, getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
     D = getattr(cfg, "head_dim", None) or cfg.hidden_size // H
@@ -315,7 +365,9 @@ def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=
     rope = ops.rope_table(Tmax, D, rope_theta_of(cfg), dev)
     scale = D ** -0.5
     if cache == "lowrank":
-        kv = LowRankKVCache(len(layers), B, Tmax, kv_ranks(model), dev, dtype)   # an uncompressed layer keeps K and V in its slot of the same cache
+        pairs = [_is_pair(l.self_attn.k_proj) and _is_pair(l.self_attn.v_proj) for l in layers]
+        # an uncompressed layer keeps K and V (never quantised) in its slot of the same cache
+        kv = LowRankKVCache(len(layers), B, Tmax, kv_ranks(model), dev, dtype, quant=[kv_quant if p else None for p in pairs])
         attn = [(LowRankKVAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, scale, rope, kernel) if _is_pair(a.k_proj) and _is_pair(a.v_proj)
                  else _DenseAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, scale, rope)) for a in (l.self_attn for l in layers)]
     else:

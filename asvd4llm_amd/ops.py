@@ -848,14 +848,16 @@ def _kv_cache_arg(name, c, B, dev):
     return r
 
 
-def _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv):
+def _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv, r_k=None):
+    """r_k: given when the caller has checked the cache by rules of its own (an int8 cache, K21)"""
     if q.dim() != 3 or q.dtype != torch.float16 or not q.is_contiguous():
         raise ValueError(f"{name} needs q [B, H, D] fp16 contiguous (got {tuple(q.shape)} {q.dtype})")
     B, H, D = q.shape
     dev = q.device
     if D not in (64, 128) or H < 1 or H_kv < 1 or H % H_kv:
         raise ValueError(f"{name}: head size 64 or 128 and H_kv dividing H (got D {D}, H {H}, H_kv {H_kv})")
-    r_k = _kv_cache_arg(name, ck, B, dev)
+    if r_k is None:
+        r_k = _kv_cache_arg(name, ck, B, dev)
     Tmax = ck.shape[1]
     if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous() or lens.device != dev:
         raise ValueError(f"{name} needs lens int32 [B] on the device of q")
@@ -918,6 +920,143 @@ def lowrank_kv_decode(q, ck, cv, lens, Ak, Av, H_kv, scale, bk=None, bv=None, ro
                                            _ptr(bv), _ptr(cos), _ptr(sin), L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, r_v, Tmax,
                                            ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(),
                                            _stream(q)), "asvd_lowrank_kv_decode")
+    return out
+
+
+# ---- K21: the low-rank KV cache as int8 codes (csrc/lowrank_kv_q8.hip, csrc/lowrank_kv_q8.h) -------------------------------------------
+
+KV_Q8_GROUP = 32   # latent columns per fp32 scale
+
+
+def lowrank_kv_groups(r):
+    """scales per cache row of r columns: groups of 32, a 16-wide last one when r % 32 == 16"""
+    return (int(r) + KV_Q8_GROUP - 1) // KV_Q8_GROUP
+
+
+def _kv_per_column(scales, r):
+    return scales.repeat_interleave(KV_Q8_GROUP, -1)[..., :r]
+
+
+def lowrank_kv_quant_torch(x):
+    """(codes int8 [..., r], scales fp32 [..., ceil(r / 32)]) of x [..., r], r a multiple of 16: the K21 format in torch ops, on any device,
+    bit for bit what lowrank_kv_quant writes.  x goes through fp16 first.  Per group of 32 columns: s = amax / 127 (fp32 division),
+    code = clamp(rint(x / s), -127, 127); a group of zeros has s = 0, a group with a NaN or an Inf s = NaN, both with codes 0."""
+    r = x.shape[-1]
+    if r < 16 or r % 16:
+        raise ValueError(f"lowrank_kv_quant_torch: rank {r} is not a multiple of 16")
+    ng = lowrank_kv_groups(r)
+    xf = x.half().float()
+    g = torch.nn.functional.pad(xf, (0, ng * KV_Q8_GROUP - r)).reshape(*x.shape[:-1], ng, KV_Q8_GROUP)
+    bad = ~torch.isfinite(g).all(-1)
+    amax = torch.where(torch.isfinite(g), g.abs(), torch.zeros_like(g)).amax(-1)
+    s = amax / torch.full_like(amax, 127.0)   # a tensor divisor: a Python scalar may be turned into a multiplication by 1 / 127
+    zero = bad | (amax == 0)
+    sd = torch.where(zero, torch.ones_like(s), s)
+    codes = torch.round(g / sd[..., None]).clamp(-127.0, 127.0)
+    codes = torch.where(zero[..., None], torch.zeros_like(codes), codes).to(torch.int8)
+    s = torch.where(bad, torch.full_like(s, float("nan")), s)
+    return codes.reshape(*x.shape[:-1], ng * KV_Q8_GROUP)[..., :r].contiguous(), s
+
+
+def lowrank_kv_dequant(codes, scales):
+    """fp16 [..., r] = fp16(float(code) * s): the value every K21 kernel uses for a code, any int8 code, any device"""
+    r = codes.shape[-1]
+    if codes.dtype != torch.int8 or scales.dtype != torch.float32 or scales.shape[:-1] != codes.shape[:-1] or scales.shape[-1] < lowrank_kv_groups(r):
+        raise ValueError(f"lowrank_kv_dequant: codes int8 [..., r] and scales fp32 [..., >= ceil(r / 32)] (got {tuple(codes.shape)} {codes.dtype}, "
+                         f"{tuple(scales.shape)} {scales.dtype})")
+    return (codes.float() * _kv_per_column(scales[..., :lowrank_kv_groups(r)], r)).half()
+
+
+def _kv_q8_arg(name, codes, scales, B, dev):
+    """the rules of an int8 cache [B, Tmax, r] and its scales [B, Tmax, >= ng]; returns r"""
+    if codes.dim() != 3 or codes.dtype != torch.int8 or codes.shape[0] != B or codes.stride(2) != 1 or codes.device != dev:
+        raise ValueError(f"{name}: codes [B, Tmax, r] int8 with unit rank stride on the device of q (got {tuple(codes.shape)} {codes.dtype})")
+    r = codes.shape[2]
+    if r < 16 or r % 16:
+        raise ValueError(f"{name}: rank {r} is not a multiple of 16")
+    if codes.data_ptr() % 16 or codes.stride(1) % 16 or codes.stride(0) % 16 or codes.stride(1) < r:
+        raise ValueError(f"{name}: code rows must be 16-byte aligned (row stride {codes.stride(1)}, batch stride {codes.stride(0)} bytes)")
+    if scales.dim() != 3 or scales.dtype != torch.float32 or tuple(scales.shape[:2]) != tuple(codes.shape[:2]) or scales.shape[2] < lowrank_kv_groups(r) \
+            or scales.stride(2) != 1 or scales.stride(1) < lowrank_kv_groups(r) or scales.device != dev:
+        raise ValueError(f"{name}: scales [B, Tmax, >= {lowrank_kv_groups(r)}] fp32 with unit last stride on the device of q "
+                         f"(got {tuple(scales.shape)} {scales.dtype})")
+    return r
+
+
+def lowrank_kv_quant(x, codes_out, scales_out):
+    """codes_out int8 [B, n, r] and scales_out fp32 [B, n, >= ceil(r / 32)] (strided views: the slice [:, t0 : t0 + n] of a cache) <- the K21
+    quantisation of x [B, n, r] fp16 (asvd_lowrank_kv_quant: one launch on the current stream, no host sync; nothing outside the
+    B * n destination rows is written).  Every argument check comes before the device is asked for."""
+    if x.dim() != 3 or x.dtype != torch.float16 or x.stride(2) != 1:
+        raise ValueError(f"lowrank_kv_quant needs x [B, n, r] fp16 with unit rank stride (got {tuple(x.shape)} {x.dtype})")
+    B, n, r = x.shape
+    if B < 1 or n < 1:
+        raise ValueError("lowrank_kv_quant: no rows")
+    if tuple(codes_out.shape) != (B, n, r) or scales_out.dim() != 3:
+        raise ValueError(f"lowrank_kv_quant: codes_out {tuple(codes_out.shape)} does not match x {tuple(x.shape)}")
+    _kv_q8_arg("lowrank_kv_quant", codes_out, scales_out, B, x.device)
+    if x.data_ptr() % 16 or x.stride(1) % 8 or x.stride(0) % 8 or x.stride(1) < r:
+        raise ValueError(f"lowrank_kv_quant: rows of x must be 16-byte aligned (row stride {x.stride(1)}, batch stride {x.stride(0)} elements)")
+    _dev(x, "x")
+    lib = L.load(True)
+    with _on(x.device):
+        L.check(lib.asvd_lowrank_kv_quant(x.data_ptr(), x.stride(1), x.stride(0), codes_out.data_ptr(), codes_out.stride(1), codes_out.stride(0),
+                                          scales_out.data_ptr(), scales_out.stride(1), scales_out.stride(0), L.F16, B, n, r, _stream(x)),
+                "asvd_lowrank_kv_quant")
+    return codes_out, scales_out
+
+
+def _kv_args_q8(name, q, ck, sk, lens, Ak, bk, rope, H_kv):
+    """_kv_args for an int8 key cache: the same rules, with _kv_q8_arg's in place of the fp16 cache's"""
+    if q.dim() != 3:
+        raise ValueError(f"{name} needs q [B, H, D] fp16 contiguous (got {tuple(q.shape)} {q.dtype})")
+    return _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv, r_k=_kv_q8_arg(name, ck, sk, q.shape[0], q.device))
+
+
+def lowrank_kv_scores_q8(q, ck, sk, lens, Ak, H_kv, scale, bk=None, rope=None, work=None):
+    """lowrank_kv_scores on an int8 cache: ck int8 codes [B, Tmax, r_k] and sk fp32 scales [B, Tmax, >= ceil(r_k / 32)] (K21,
+    asvd_lowrank_kv_scores_q8).  The bits of lowrank_kv_scores(q, lowrank_kv_dequant(ck, sk), ...)."""
+    B, H, D, r_k, Tmax, mode, cos, sin = _kv_args_q8("lowrank_kv_scores_q8", q, ck, sk, lens, Ak, bk, rope, H_kv)
+    _dev(q, "q")
+    lib = L.load(True)
+    dev = q.device
+    if work is None:
+        work = lowrank_kv_work(B, H, Tmax, r_k, 16, dev)
+    out = torch.empty((B, H, Tmax), dtype=torch.float32, device=dev)
+    with _on(dev):
+        L.check(lib.asvd_lowrank_kv_scores_q8(q.data_ptr(), ck.data_ptr(), sk.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin),
+                                              L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), sk.stride(1),
+                                              sk.stride(0), out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)), "asvd_lowrank_kv_scores_q8")
+    return out
+
+
+def lowrank_kv_decode_q8(q, ck, cv, sk, sv, lens, Ak, Av, H_kv, scale, bk=None, bv=None, rope=None, work=None, out=None):
+    """lowrank_kv_decode on an int8 cache: ck / cv int8 codes, sk / sv their fp32 group scales (K21, asvd_lowrank_kv_decode_q8).  The bits of
+    lowrank_kv_decode on the dequantised cache; same workspace (lowrank_kv_work), asynchronous, graph-capturable when `work` and `out` are given."""
+    name = "lowrank_kv_decode_q8"
+    B, H, D, r_k, Tmax, mode, cos, sin = _kv_args_q8(name, q, ck, sk, lens, Ak, bk, rope, H_kv)
+    dev = q.device
+    r_v = _kv_q8_arg(name, cv, sv, B, dev)
+    if cv.shape[1] != Tmax:
+        raise ValueError(f"{name}: ck and cv hold different token counts")
+    if Av.dtype != torch.float16 or tuple(Av.shape) != (H_kv * D, r_v) or not Av.is_contiguous() or Av.device != dev or Av.data_ptr() % 16:
+        raise ValueError(f"{name} needs Av [H_kv * D, r_v] fp16 contiguous (got {tuple(Av.shape)} {Av.dtype})")
+    if bv is not None and (bv.dtype != torch.float16 or bv.numel() != H_kv * D or not bv.is_contiguous() or bv.device != dev):
+        raise ValueError(f"{name} needs bv [H_kv * D] fp16 contiguous or None")
+    if out is not None and (out.dtype != torch.float16 or tuple(out.shape) != (B, H, D) or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"{name}: out must be [B, H, D] fp16 contiguous on the device of q")
+    _dev(q, "q")
+    lib = L.load(True)
+    if work is None:
+        work = lowrank_kv_work(B, H, Tmax, r_k, r_v, dev)
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float16, device=dev)
+    with _on(dev):
+        L.check(lib.asvd_lowrank_kv_decode_q8(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), sk.data_ptr(), sv.data_ptr(), lens.data_ptr(), Ak.data_ptr(),
+                                              Av.data_ptr(), _ptr(bk), _ptr(bv), _ptr(cos), _ptr(sin), L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D,
+                                              r_k, r_v, Tmax, ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0), sk.stride(1), sk.stride(0),
+                                              sv.stride(1), sv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)),
+                "asvd_lowrank_kv_decode_q8")
     return out
 
 

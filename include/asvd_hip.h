@@ -600,6 +600,36 @@ int asvd_lowrank_kv_decode(const void* q, const void* ck, const void* cv, const 
                            int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
                            int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K21: the low-rank KV cache as int8 codes (csrc/lowrank_kv_q8.hip, csrc/lowrank_kv_q8.h, DESIGN.md 4 "K21").
+ * A cache row x[0 .. r) (r a multiple of 16) is cut into groups of 32 consecutive columns (a 16-wide last group when r % 32 == 16),
+ * ng = ceil(r / 32) groups.  Per group amax = max |x|, s = amax / 127.0f (IEEE fp32), code = clamp(rintf(float(x) / s), -127, 127).
+ * A group of zeros has s = 0 and codes 0; a group that holds a NaN or an Inf has s = NaN and codes 0.  The value a kernel uses is
+ * d = fp16_rne(float(code) * s): one fp32 product, one rounding.
+ * Layout: codes int8 [B, Tmax, r], unit column stride, row and batch strides (in BYTES) multiples of 16, 16-byte aligned base;
+ * scales fp32 [B, Tmax, >= ng], unit last stride, row and batch strides in FLOATS, 4-byte aligned base.
+ *   asvd_lowrank_kv_quant      x fp16 [B, n, r] (strides in elements, multiples of 8, 16-byte aligned base) -> codes and scales of the
+ *                              B * n destination rows (the slice [:, t0 : t0 + n] of a cache: pass its first row and the cache's strides).
+ *                              One launch, no host sync, no atomics; nothing outside those rows is written.
+ *   asvd_lowrank_kv_scores_q8  asvd_lowrank_kv_scores / _decode with ck / cv holding codes and sk / sv their scales.  The kernels load codes
+ *   asvd_lowrank_kv_decode_q8  and scales, dequantise in registers and feed the same products in the same order: the result has the bits of the
+ *                              fp16 entry called on the dequantised cache.  Same workspace (asvd_lowrank_kv_worksize), same masking: nothing at
+ *                              positions >= lens[b], code or scale, reaches an output.
+ * dtype ASVD_F16 only.  A NULL or misaligned pointer, a rank that is no multiple of 16, a code stride that is no multiple of 16, a scale
+ * row shorter than ng, a key bias under rotation and every rule of the fp16 entries are ASVD_E_BADARG before any device call. */
+int asvd_lowrank_kv_quant(const void* x, int64_t x_row_stride, int64_t x_batch_stride, void* codes, int64_t c_row_stride, int64_t c_batch_stride,
+                          void* scales, int64_t s_row_stride, int64_t s_batch_stride, int dtype, int64_t B, int64_t n, int64_t r, void* stream);
+int asvd_lowrank_kv_scores_q8(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                              const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k,
+                              int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride,
+                              void* scores_out, void* work, size_t work_bytes, void* stream);
+int asvd_lowrank_kv_decode_q8(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
+                              const void* Av, const void* bk, const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode,
+                              float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax,
+                              int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride, int64_t cv_batch_stride, int64_t sk_row_stride,
+                              int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work, size_t work_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

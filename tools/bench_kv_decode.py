@@ -10,7 +10,12 @@ layer would time the cache).  One pass = the call on every layer.  The two passe
 --warmup; median / min / max per LAYER in microseconds.  "eager" is the call as a user makes it (host work included), "graph" one pass captured
 into a device graph and replayed (what the device does; also the evidence that the K20 sequence is capturable).  Also: the cache bytes per
 token and layer of both, the algorithmic bytes and flops of the K20 step, and the largest difference of the two outputs relative to the largest
-output (both are fp16 routes to the same value)."""
+output (both are fp16 routes to the same value).
+
+--quant int8 adds a third pass per shape: the same latents as int8 codes and one fp32 scale per token and 32 columns (K21: quantised by
+asvd_lowrank_kv_quant, decoded by asvd_lowrank_kv_decode_q8), alternating with the other two, eager and graph-replayed; its cache bytes per token,
+its time over the fp16 low-rank route's of the same run, and the largest difference of its output from the fp16 low-rank route's.  The run that
+profiles/lowrank_kv_q8.json holds: python tools/bench_kv_decode.py --quant int8 > profiles/lowrank_kv_q8.json"""
 import argparse
 import json
 import os
@@ -79,6 +84,15 @@ def one_shape(dev, H, D, r, T, B, mode, args):
             K = rotate_half(K.float(), rope[0][None, :, None, :], rope[1][None, :, None, :]).half()
         Ks.append(K.transpose(1, 2).contiguous())
         Vs.append(F.linear(cv[-1], Av).view(B, T, H, D).transpose(1, 2).contiguous())
+    q8 = []
+    if args.quant == "int8":
+        for i in range(layers):
+            t = [torch.empty(B, T, r, dtype=torch.int8, device=dev), torch.empty(B, T, r, dtype=torch.int8, device=dev),
+                 torch.empty(B, T, ops.lowrank_kv_groups(r), dtype=torch.float32, device=dev),
+                 torch.empty(B, T, ops.lowrank_kv_groups(r), dtype=torch.float32, device=dev)]
+            ops.lowrank_kv_quant(ck[i], t[0], t[2])
+            ops.lowrank_kv_quant(cv[i], t[1], t[3])
+            q8.append(t)
     work = ops.lowrank_kv_work(B, H, T, r, r, dev)
     out = torch.empty(B, H, D, dtype=torch.float16, device=dev)
     q4 = q[:, :, None, :]
@@ -86,6 +100,10 @@ def one_shape(dev, H, D, r, T, B, mode, args):
     def k20():
         for i in range(layers):
             ops.lowrank_kv_decode(q, ck[i], cv[i], lens, Ak, Av, H, scale, rope=rope, work=work, out=out)
+
+    def k21():
+        for c_k, c_v, s_k, s_v in q8:
+            ops.lowrank_kv_decode_q8(q, c_k, c_v, s_k, s_v, lens, Ak, Av, H, scale, rope=rope, work=work, out=out)
 
     def dense():
         for i in range(layers):
@@ -101,12 +119,24 @@ def one_shape(dev, H, D, r, T, B, mode, args):
     rec["k20_bytes"] = B * T * 2 * r * 2 + 2 * H * D * r * 2 + 2 * B * H * T * 4
     rec["k20_flops"] = (2 * B * T * r * H * D + 2 * B * T * H * D if mode == "half" else 2 * B * H * D * r + 2 * B * T * r * H) \
         + 2 * B * T * r * H + 2 * B * H * D * r
-    e = time_alternating([k20, dense], args.warmup, args.iters)
+    routes = [k20, dense]
+    if q8:
+        routes.append(k21)
+        got8 = ops.lowrank_kv_decode_q8(q, *q8[0], lens, Ak, Av, H, scale, rope=rope).float()
+        rec["cache_bytes_per_token_layer"]["lowrank_int8"] = 2 * (r + 4 * ops.lowrank_kv_groups(r))
+        rec["int8_max_diff_from_lowrank_over_max_out"] = float((got8 - got).abs().max() / ref.abs().max())
+    e = time_alternating(routes, args.warmup, args.iters)
     rec["eager"] = {"k20": stats(e[0], layers), "dense": stats(e[1], layers)}
+    if q8:
+        rec["eager"]["k21_int8"] = stats(e[2], layers)
+        rec["int8_over_lowrank_eager"] = round(rec["eager"]["k21_int8"]["median_us"] / rec["eager"]["k20"]["median_us"], 3)
     try:
-        reps = [capture(k20), capture(dense)]
+        reps = [capture(f) for f in routes]
         gm = time_alternating(reps, args.warmup, args.iters)
         rec["graph"] = {"k20": stats(gm[0], layers), "dense": stats(gm[1], layers)}
+        if q8:
+            rec["graph"]["k21_int8"] = stats(gm[2], layers)
+            rec["int8_over_lowrank_graph"] = round(rec["graph"]["k21_int8"]["median_us"] / rec["graph"]["k20"]["median_us"], 3)
         rec["k20_over_dense_graph"] = round(rec["graph"]["k20"]["median_us"] / rec["graph"]["dense"]["median_us"], 3)
         rec["k20_GBps_graph"] = round(rec["k20_bytes"] / rec["graph"]["k20"]["median_us"] / 1e3, 1)
     except Exception as ex:   # reported, not hidden: the eager figures stand alone then
@@ -126,6 +156,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max_layers", type=int, default=16)
+    ap.add_argument("--quant", choices=["none", "int8"], default="none", help="int8: a third pass on the int8 form of the low-rank cache (K21)")
     args = ap.parse_args()
     L.load(require_device=True)
     dev = torch.device("cuda", 0)
@@ -138,8 +169,8 @@ def main():
                         recs.append(one_shape(dev, H, args.head_dim, r, T, B, mode, args))
                         print(f"[bench_kv_decode] {json.dumps(recs[-1])}", file=sys.stderr, flush=True)
                         torch.cuda.empty_cache()
-    print(json.dumps({"bench": "kv_decode", "device": torch.cuda.get_device_name(0), "runs": 1, "iters_per_run": args.iters, "warmup": args.warmup,
-                      "timing": "device events around one pass over `layers` layers, K20 and dense alternating; per-layer microseconds",
+    print(json.dumps({"bench": "kv_decode", "device": torch.cuda.get_device_name(0), "runs": 1, "iters_per_run": args.iters, "warmup": args.warmup, "quant": args.quant,
+                      "timing": "device events around one pass over `layers` layers, the routes alternating; per-layer microseconds",
                       "results": recs}))
 
 
