@@ -77,8 +77,9 @@ def run_kv_cache_decode(model, calib_loader, args):
     """--kv_cache_decode_tokens N: what the compressed k_proj / v_proj buy at run time.  Prints the bytes one token occupies in the ordinary
     and in the low-rank KV cache (all layers), then greedy-decodes N tokens from the first calibration sample on both caches (K20 on the low-rank
     one, asvd4llm_amd/kv_cache.py) and prints the largest difference of their logits.  --kv_cache_quant int8 adds the int8 form of the low-rank
-    cache (K21): its bytes per token, and the same forced token stream decoded on it."""
-    from asvd4llm_amd.kv_cache import greedy_decode, is_llama_family, kv_ranks
+    cache (K21): its bytes per token, and the same forced token stream decoded on it.  One line says which route the decode steps on the
+    low-rank cache take: the kernel, or the reason LowRankKVAttention refuses it (a bf16 model: "not fp16" unless ASVD_KV_BF16=1, K22)."""
+    from asvd4llm_amd.kv_cache import decode_routes, greedy_decode, is_llama_family, kv_ranks
     from asvd4llm_amd.ops import lowrank_kv_groups
     dense = 0
     ranks, pairs = {}, {}
@@ -106,6 +107,10 @@ def run_kv_cache_decode(model, calib_loader, args):
         return
     ids = calib_loader[0]["input_ids"][:, :64].to(next(model.parameters()).device)
     n = int(args.kv_cache_decode_tokens)
+    routes = decode_routes(model)
+    print("kv cache decode route: " + ", ".join(f"{r} ({routes.count(r)} layers)" for r in dict.fromkeys(routes))
+          + "  [kernel: K20 on the low-rank cache; anything else names why a layer's decode steps stay in torch"
+          + ("; a bf16 model takes the kernel with ASVD_KV_BF16=1" if "not fp16" in routes else "") + "]")
     toks_low, logits_low = greedy_decode(model, ids, n, cache="lowrank")
     toks_dense, logits_dense = greedy_decode(model, ids, n, cache="dense", forced=toks_low)
     diff = (logits_low.float() - logits_dense.float()).abs().max().item()

@@ -87,6 +87,14 @@ SIGNATURES = {
                                        _vp, _sz, _vp]),
     "asvd_lowrank_kv_decode_q8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                        _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "asvd_lowrank_kv_scores_a16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz,
+                                        _vp]),
+    "asvd_lowrank_kv_decode_a16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                        _i64, _i64, _vp, _vp, _sz, _vp]),
+    "asvd_lowrank_kv_scores_q8_a16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                           _vp, _vp, _sz, _vp]),
+    "asvd_lowrank_kv_decode_q8_a16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i64, _i64, _i64, _i64, _i64, _i64,
+                                           _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_fro_worksize":(_i, [_i64, _i64, _c.POINTER(_sz)]),
     "asvd_fro_norm_sq": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _sz, _vp]),
     "asvd_reconstruct_worksize": (_i, [_i64, _i64, _i64, _c.POINTER(_sz)]),

@@ -29,6 +29,12 @@
 // dequantises them in registers, d = fp16(float(code) * s).  The fp16 values then feed the same MFMA in the same order, so an int8 call
 // returns the bits of the fp16 call on the dequantised cache.  Masked tokens load code AND scale from the clamped address and are replaced
 // by 0 with the same select.  Stages a and d, the plan and the workspace do not depend on the cache format.
+//
+// K22: every stage is templated on the 16-bit element type ADT (ASVD_F16 or ASVD_BF16: the type of q, A_k, A_v, the biases, the output and of an
+// unquantised cache), reached through the asvd_lowrank_kv_*_a16 entries.  The bf16 form is the same text with bf16 loads, one RNE rounding to
+// bf16 wherever the fp16 form rounds to fp16 (q~, p, out) and v_mfma_f32_32x32x16_bf16, whose operand and accumulator layout is the fp16
+// instruction's; plan, workspace, geometry, masking and the order of every sum are shared.  On an int8 cache the bf16 form uses
+// bf16_rne(fp16_rne(float(code) * s)): K21's value, rounded once more (what cache.read(..., torch.bfloat16) hands the torch path).
 #include "lowrank_kv_q8.h"
 
 namespace {
@@ -70,59 +76,83 @@ __device__ __forceinline__ int kv_len(const int* __restrict__ lens, int b, int T
 // accumulator register q of lane half g -> row of the 32 x 32 tile (the column is lane & 31)
 __device__ __forceinline__ int acc_row(int q, int g) { return (q & 3) + 8 * (q >> 2) + 4 * g; }
 
-// ---- a: q~ = fp16(A_k[kv(h)]^T q) ------------------------------------------------------------------------------------------------
+// ---- ADT, the 16-bit element type: the two forms differ in these three helpers (element load, RNE rounding, matrix instruction) only ----
+typedef __bf16 kv_bf16x8 __attribute__((ext_vector_type(8)));
+template <int ADT>
+__device__ __forceinline__ float kv_to_f32(uint16_t b) {
+    return ADT == ASVD_BF16 ? bf16_bits_to_f32(b) : f16_bits_to_f32(b);
+}
+template <int ADT>
+__device__ __forceinline__ uint16_t kv_from_f32(float v) {
+    return ADT == ASVD_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
+}
+// a, b: 8 values of type ADT each; f16x8 is their container in both forms
+template <int ADT>
+__device__ __forceinline__ f32x16 kv_mfma(f16x8 a, f16x8 b, f32x16 acc) {
+    if constexpr (ADT == ASVD_BF16)
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kv_bf16x8, a), __builtin_bit_cast(kv_bf16x8, b), acc, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+}
+
+// ---- a: q~ = ADT(A_k[kv(h)]^T q) -------------------------------------------------------------------------------------------------
+template <int ADT>
 __global__ __launch_bounds__(256) void kv_qtilde_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ Ak, uint16_t* __restrict__ qt,
                                                         int H, int group, int D, int r_k, int hpad) {
     __shared__ float qs[128];
     const int b = blockIdx.x / H, h = blockIdx.x % H, kvh = h / group, tid = threadIdx.x;
-    if (tid < D) qs[tid] = f16_bits_to_f32(q[((int64_t)b * H + h) * D + tid]);
+    if (tid < D) qs[tid] = kv_to_f32<ADT>(q[((int64_t)b * H + h) * D + tid]);
     __syncthreads();
     const int j = blockIdx.y * 256 + tid;
     if (j >= r_k) return;
     const uint16_t* a = Ak + (int64_t)kvh * D * r_k + j;
     float acc = 0.f;
-    for (int d = 0; d < D; ++d) acc += f16_bits_to_f32(a[(int64_t)d * r_k]) * qs[d];
-    qt[((int64_t)b * hpad + h) * r_k + j] = f32_to_f16_bits(acc);
+    for (int d = 0; d < D; ++d) acc += kv_to_f32<ADT>(a[(int64_t)d * r_k]) * qs[d];
+    qt[((int64_t)b * hpad + h) * r_k + j] = kv_from_f32<ADT>(acc);
 }
 
-// ---- how a lane obtains its cache operand: Q8 = false reads fp16 values, Q8 = true int8 codes and their group scales (K21) -------------
+// ---- how a lane obtains its cache operand: Q8 = false reads ADT values, Q8 = true int8 codes and their group scales (K21) --------------
 // stage b: the 8 rank columns 16 k + 8 g .. + 7 of token t; they lie in ONE 32-column group, k >> 1
-template <bool Q8> struct KvTok;
-template <> struct KvTok<false> {
+template <int ADT, bool Q8> struct KvTok;
+template <int ADT> struct KvTok<ADT, false> {
     const uint4* p;
     __device__ __forceinline__ KvTok(const void* c, int64_t rs, int64_t bs, const float*, int64_t, int64_t, int b, int t, int g)
         : p((const uint4*)((const uint16_t*)c + (int64_t)b * bs + (int64_t)t * rs + 8 * g)) {}
     __device__ __forceinline__ f16x8 operator()(int k) const { return __builtin_bit_cast(f16x8, p[2 * k]); }
 };
-template <> struct KvTok<true> {
+template <int ADT> struct KvTok<ADT, true> {
     const uint2* p;
     const float* s;
     __device__ __forceinline__ KvTok(const void* c, int64_t rs, int64_t bs, const float* sc, int64_t srs, int64_t sbs, int b, int t, int g)
         : p((const uint2*)((const int8_t*)c + (int64_t)b * bs + (int64_t)t * rs + 8 * g)), s(sc + (int64_t)b * sbs + (int64_t)t * srs) {}
-    __device__ __forceinline__ f16x8 operator()(int k) const { return kv_q8_dequant8(p[2 * k], s[k >> 1]); }
+    __device__ __forceinline__ f16x8 operator()(int k) const {
+        if constexpr (ADT == ASVD_BF16) return kv_q8_dequant8_bf16(p[2 * k], s[k >> 1]);
+        else return kv_q8_dequant8(p[2 * k], s[k >> 1]);
+    }
 };
-// stage c: rank column j of any token t (the bits of the fp16 value)
-template <bool Q8> struct KvCol;
-template <> struct KvCol<false> {
+// stage c: rank column j of any token t (the bits of the ADT value)
+template <int ADT, bool Q8> struct KvCol;
+template <int ADT> struct KvCol<ADT, false> {
     const uint16_t* p;
     int64_t rs;
     __device__ __forceinline__ KvCol(const void* c, int64_t rs_, int64_t bs, const float*, int64_t, int64_t, int b, int j)
         : p((const uint16_t*)c + (int64_t)b * bs + j), rs(rs_) {}
     __device__ __forceinline__ uint16_t operator()(int t) const { return p[(int64_t)t * rs]; }
 };
-template <> struct KvCol<true> {
+template <int ADT> struct KvCol<ADT, true> {
     const int8_t* p;
     const float* s;
     int64_t rs, srs;
     __device__ __forceinline__ KvCol(const void* c, int64_t rs_, int64_t bs, const float* sc, int64_t srs_, int64_t sbs, int b, int j)
         : p((const int8_t*)c + (int64_t)b * bs + j), s(sc + (int64_t)b * sbs + j / KV_Q8_GROUP), rs(rs_), srs(srs_) {}
     __device__ __forceinline__ uint16_t operator()(int t) const {
-        return __builtin_bit_cast(uint16_t, kv_q8_dequant((int)p[(int64_t)t * rs], s[(int64_t)t * srs]));
+        if constexpr (ADT == ASVD_BF16) return kv_q8_dequant_bf16((int)p[(int64_t)t * rs], s[(int64_t)t * srs]);
+        else return __builtin_bit_cast(uint16_t, kv_q8_dequant((int)p[(int64_t)t * rs], s[(int64_t)t * srs]));
     }
 };
 
 // ---- b, no rotation: S = scale * q~ C_k^T, heads in the accumulator registers, tokens on the lanes (coalesced stores) -----------------
-template <bool Q8>
+template <int ADT, bool Q8>
 __global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __restrict__ qt, const void* __restrict__ ck, int64_t rs, int64_t bs,
                                                              const float* __restrict__ sk, int64_t srs, int64_t sbs, const int* __restrict__ lens,
                                                              float* __restrict__ S, float scale, int H, int r_k, int Tmax, int hpad, int tld) {
@@ -131,13 +161,13 @@ __global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __r
     const int t0 = blockIdx.y * KV_TOK_TILE + wave * 32, h0 = blockIdx.z * 32;
     if (t0 >= len) return;
     const uint4* qp = (const uint4*)(qt + ((int64_t)b * hpad + min(h0 + i, H - 1)) * r_k + 8 * g);
-    const KvTok<Q8> cp(ck, rs, bs, sk, srs, sbs, b, min(t0 + i, len - 1), g);
+    const KvTok<ADT, Q8> cp(ck, rs, bs, sk, srs, sbs, b, min(t0 + i, len - 1), g);
     f32x16 acc;
 #pragma unroll
     for (int x = 0; x < 16; ++x) acc[x] = 0.f;
     const int nk = r_k / 16;
     for (int k = 0; k < nk; ++k)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, qp[2 * k]), cp(k), acc, 0, 0, 0);
+        acc = kv_mfma<ADT>(__builtin_bit_cast(f16x8, qp[2 * k]), cp(k), acc);
     const int t = t0 + i;
     if (t < len) {
 #pragma unroll
@@ -152,7 +182,7 @@ __global__ __launch_bounds__(256) void kv_scores_none_kernel(const uint16_t* __r
 // Feature d of the tile sits in register x of accumulator n with d = 32 n + acc_row(x, g), so the partner d + D/2 of the rotation is
 // register x of accumulator n + D/64 of the SAME lane: the rotation needs no lane movement, the dot over d is a sum over registers plus
 // one exchange between the two lane halves.  All heads of a KV group reuse the rotated tile.
-template <int D, bool Q8>
+template <int ADT, int D, bool Q8>
 __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __restrict__ q, const void* __restrict__ ck, int64_t rs, int64_t bs,
                                                              const float* __restrict__ sk, int64_t srs, int64_t sbs,
                                                              const int* __restrict__ lens, const uint16_t* __restrict__ Ak,
@@ -164,7 +194,7 @@ __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __r
     const int t0 = blockIdx.y * KV_TOK_TILE + wave * 32;
     if (t0 >= len) return;
     const int tc = min(t0 + i, len - 1);   // masked lanes work on a valid token and store nothing
-    const KvTok<Q8> cp(ck, rs, bs, sk, srs, sbs, b, tc, g);
+    const KvTok<ADT, Q8> cp(ck, rs, bs, sk, srs, sbs, b, tc, g);
     const uint4* ap = (const uint4*)(Ak + ((int64_t)kvh * D + i) * r_k + 8 * g);
     const int64_t astep = (int64_t)32 * r_k / 8;   // 32 feature rows, in uint4
     f32x16 acc[NT];
@@ -177,7 +207,7 @@ __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __r
         const f16x8 c = cp(k);
 #pragma unroll
         for (int n = 0; n < NT; ++n)
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ap[n * astep + 2 * k]), c, acc[n], 0, 0, 0);
+            acc[n] = kv_mfma<ADT>(__builtin_bit_cast(f16x8, ap[n * astep + 2 * k]), c, acc[n]);
     }
     // rotate in place: (lo, hi) <- (lo cos - hi sin, hi cos + lo sin), table row tc, column d of the low half
     const float* crow = cs + (int64_t)tc * (D / 2);
@@ -205,10 +235,10 @@ __global__ __launch_bounds__(256) void kv_scores_half_kernel(const uint16_t* __r
 #pragma unroll
             for (int x4 = 0; x4 < 4; ++x4) {
                 const uint2 qv = *(const uint2*)(qh + 32 * n + 8 * x4 + 4 * g);
-                part += acc[n][4 * x4 + 0] * f16_bits_to_f32((uint16_t)(qv.x & 0xffffu));
-                part += acc[n][4 * x4 + 1] * f16_bits_to_f32((uint16_t)(qv.x >> 16));
-                part += acc[n][4 * x4 + 2] * f16_bits_to_f32((uint16_t)(qv.y & 0xffffu));
-                part += acc[n][4 * x4 + 3] * f16_bits_to_f32((uint16_t)(qv.y >> 16));
+                part += acc[n][4 * x4 + 0] * kv_to_f32<ADT>((uint16_t)(qv.x & 0xffffu));
+                part += acc[n][4 * x4 + 1] * kv_to_f32<ADT>((uint16_t)(qv.x >> 16));
+                part += acc[n][4 * x4 + 2] * kv_to_f32<ADT>((uint16_t)(qv.y & 0xffffu));
+                part += acc[n][4 * x4 + 3] * kv_to_f32<ADT>((uint16_t)(qv.y >> 16));
             }
         const float other = __shfl_xor(part, 32, 64);
         const float tot = g == 0 ? part + other : other + part;   // lower half first in both halves
@@ -225,7 +255,7 @@ __global__ __launch_bounds__(256) void kv_scores_copy_kernel(const float* __rest
 }
 
 // ---- c: one split of the tokens.  m, l and O~[32 heads, 32 ranks per wave] = p C_v ------------------------------------------------------
-template <bool Q8>
+template <int ADT, bool Q8>
 __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S, const void* __restrict__ cv, int64_t rs, int64_t bs,
                                                     const float* __restrict__ sv, int64_t srs, int64_t sbs, const int* __restrict__ lens, float* __restrict__ ml, float* __restrict__ Op, int H, int r_v,
                                                     int Tmax, int hpad, int tld, int L, int ns) {
@@ -249,8 +279,8 @@ __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S,
             if (tt + u < end) m = fmaxf(m, v[u]);
     }
     m = fmaxf(m, __shfl_xor(m, 32, 64));
-    // pass 2: p = fp16(exp(S - m)) is the A operand (row = head i, k = token), C_v the B operand (k = token, column = rank j0 + i)
-    const KvCol<Q8> vcol(cv, rs, bs, sv, srs, sbs, b, min(j0 + i, r_v - 1));
+    // pass 2: p = ADT(exp(S - m)) is the A operand (row = head i, k = token), C_v the B operand (k = token, column = rank j0 + i)
+    const KvCol<ADT, Q8> vcol(cv, rs, bs, sv, srs, sbs, b, min(j0 + i, r_v - 1));
     f32x16 acc;
 #pragma unroll
     for (int x = 0; x < 16; ++x) acc[x] = 0.f;
@@ -263,13 +293,13 @@ __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S,
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const bool live = tt + u < end;
-            const _Float16 p = live ? (_Float16)expf(v[u] - m) : (_Float16)0.f;
-            l += (float)p;
-            pf[u] = p;
+            const uint16_t p = live ? kv_from_f32<ADT>(expf(v[u] - m)) : (uint16_t)0;   // l sums the ROUNDED p
+            l += kv_to_f32<ADT>(p);
+            pf[u] = __builtin_bit_cast(_Float16, p);
             const uint16_t c = vcol(min(tt + u, end - 1));
             vf[u] = __builtin_bit_cast(_Float16, (uint16_t)(live ? c : (uint16_t)0));
         }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(pf, vf, acc, 0, 0, 0);
+        acc = kv_mfma<ADT>(pf, vf, acc);
     }
     const float lo = __shfl_xor(l, 32, 64);
     l = g == 0 ? l + lo : lo + l;
@@ -288,6 +318,7 @@ __global__ __launch_bounds__(256) void kv_pv_kernel(const float* __restrict__ S,
 }
 
 // ---- d: merge the live splits in index order, up-project through A_v, add b_v, round once ----------------------------------------------
+template <int ADT>
 __global__ __launch_bounds__(256) void kv_combine_kernel(const float* __restrict__ ml, const float* __restrict__ Op, const int* __restrict__ lens,
                                                          const uint16_t* __restrict__ Av, const uint16_t* __restrict__ bv, uint16_t* __restrict__ out,
                                                          int H, int group, int D, int r_v, int Tmax, int hpad, int L, int ns) {
@@ -328,20 +359,20 @@ __global__ __launch_bounds__(256) void kv_combine_kernel(const float* __restrict
         for (int c = lane; c < r_v / 8; c += 64) {
             const uint4 a = arow[c];
             const float4 o0 = *(const float4*)(osum + 8 * c), o1 = *(const float4*)(osum + 8 * c + 4);
-            acc += f16_bits_to_f32((uint16_t)(a.x & 0xffffu)) * o0.x;
-            acc += f16_bits_to_f32((uint16_t)(a.x >> 16)) * o0.y;
-            acc += f16_bits_to_f32((uint16_t)(a.y & 0xffffu)) * o0.z;
-            acc += f16_bits_to_f32((uint16_t)(a.y >> 16)) * o0.w;
-            acc += f16_bits_to_f32((uint16_t)(a.z & 0xffffu)) * o1.x;
-            acc += f16_bits_to_f32((uint16_t)(a.z >> 16)) * o1.y;
-            acc += f16_bits_to_f32((uint16_t)(a.w & 0xffffu)) * o1.z;
-            acc += f16_bits_to_f32((uint16_t)(a.w >> 16)) * o1.w;
+            acc += kv_to_f32<ADT>((uint16_t)(a.x & 0xffffu)) * o0.x;
+            acc += kv_to_f32<ADT>((uint16_t)(a.x >> 16)) * o0.y;
+            acc += kv_to_f32<ADT>((uint16_t)(a.y & 0xffffu)) * o0.z;
+            acc += kv_to_f32<ADT>((uint16_t)(a.y >> 16)) * o0.w;
+            acc += kv_to_f32<ADT>((uint16_t)(a.z & 0xffffu)) * o1.x;
+            acc += kv_to_f32<ADT>((uint16_t)(a.z >> 16)) * o1.y;
+            acc += kv_to_f32<ADT>((uint16_t)(a.w & 0xffffu)) * o1.z;
+            acc += kv_to_f32<ADT>((uint16_t)(a.w >> 16)) * o1.w;
         }
         acc = wave_reduce_sum(acc);
         if (lane == 0) {
             float v = acc * inv;
-            if (bv) v += f16_bits_to_f32(bv[kvh * D + d]);
-            orow[d] = f32_to_f16_bits(v);
+            if (bv) v += kv_to_f32<ADT>(bv[kvh * D + d]);
+            orow[d] = kv_from_f32<ADT>(v);
         }
     }
 }
@@ -351,9 +382,9 @@ inline bool mis16(const void* p) { return ((uintptr_t)p & 15) != 0; }
 // the argument rules shared by both entries; nothing here touches the device
 int kv_check_common(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cs, const void* sn, int dtype,
                     int rope_mode, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax, int64_t ck_rs, int64_t ck_bs,
-                    const void* work, int64_t unit = 8) {   // unit: cache elements in 16 bytes (8 fp16 values, 16 int8 codes)
+                    const void* work, int64_t unit = 8) {   // unit: cache elements in 16 bytes (8 fp16 / bf16 values, 16 int8 codes)
     if (!q || !ck || !lens || !Ak || !work) return ASVD_E_BADARG;
-    if (dtype != ASVD_F16) return ASVD_E_BADARG;
+    if (dtype != ASVD_F16 && dtype != ASVD_BF16) return ASVD_E_BADARG;
     if (rope_mode != ASVD_KV_ROPE_NONE && rope_mode != ASVD_KV_ROPE_HALF) return ASVD_E_BADARG;
     if (D != 64 && D != 128) return ASVD_E_BADARG;
     if (B < 1 || B > (1 << 20) || H < 1 || H > 4096 || H_kv < 1 || H % H_kv || Tmax < 1 || Tmax > (1 << 22)) return ASVD_E_BADARG;
@@ -381,7 +412,7 @@ int kv_check_scales(const void* s, int64_t B, int64_t r, int64_t Tmax, int64_t s
     return ASVD_OK;
 }
 
-template <bool Q8>
+template <int ADT, bool Q8>
 int kv_scores_launch(const KvPlan& p, const void* q, const void* ck, const void* lens, const void* Ak, const void* cs, const void* sn, int rope_mode,
                      float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax, int64_t ck_rs, int64_t ck_bs, const float* sk,
                      int64_t sk_rs, int64_t sk_bs, void* work, hipStream_t st) {
@@ -389,16 +420,16 @@ int kv_scores_launch(const KvPlan& p, const void* q, const void* ck, const void*
     float* S = (float*)((char*)work + p.off_s);
     const int group = (int)(H / H_kv), ntile = (int)ceil_div64(Tmax, KV_TOK_TILE);
     if (rope_mode == ASVD_KV_ROPE_NONE) {
-        hipLaunchKernelGGL(kv_qtilde_kernel, dim3((unsigned)(B * H), (unsigned)ceil_div64(r_k, 256)), dim3(256), 0, st, (const uint16_t*)q,
+        hipLaunchKernelGGL((kv_qtilde_kernel<ADT>), dim3((unsigned)(B * H), (unsigned)ceil_div64(r_k, 256)), dim3(256), 0, st, (const uint16_t*)q,
                            (const uint16_t*)Ak, qt, (int)H, group, (int)D, (int)r_k, (int)p.hpad);
-        hipLaunchKernelGGL((kv_scores_none_kernel<Q8>), dim3((unsigned)B, ntile, (unsigned)(p.hpad / 32)), dim3(256), 0, st, (const uint16_t*)qt,
+        hipLaunchKernelGGL((kv_scores_none_kernel<ADT, Q8>), dim3((unsigned)B, ntile, (unsigned)(p.hpad / 32)), dim3(256), 0, st, (const uint16_t*)qt,
                            ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, S, scale, (int)H, (int)r_k, (int)Tmax, (int)p.hpad, (int)p.tld);
     } else if (D == 64) {
-        hipLaunchKernelGGL((kv_scores_half_kernel<64, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
+        hipLaunchKernelGGL((kv_scores_half_kernel<ADT, 64, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
                            ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
                            (int)H, group, (int)r_k, (int)Tmax, (int)p.tld);
     } else {
-        hipLaunchKernelGGL((kv_scores_half_kernel<128, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
+        hipLaunchKernelGGL((kv_scores_half_kernel<ADT, 128, Q8>), dim3((unsigned)B, ntile, (unsigned)H_kv), dim3(256), 0, st, (const uint16_t*)q,
                            ck, ck_rs, ck_bs, sk, sk_rs, sk_bs, (const int*)lens, (const uint16_t*)Ak, (const float*)cs, (const float*)sn, S, scale,
                            (int)H, group, (int)r_k, (int)Tmax, (int)p.tld);
     }
@@ -418,14 +449,40 @@ int kv_scores_entry(const void* q, const void* ck, const void* sk, const void* l
     if (scores_out && ((uintptr_t)scores_out & 3)) return ASVD_E_BADARG;
     const KvPlan p = kv_plan(B, H, Tmax, r_k, 16);
     if (work_bytes < p.off_ml) return ASVD_E_WORKSPACE;   // q~ and S only
-    const int lrc = kv_scores_launch<Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
-                                         ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, (hipStream_t)stream);
+    const int lrc = dtype == ASVD_BF16
+                        ? kv_scores_launch<ASVD_BF16, Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                                          ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, (hipStream_t)stream)
+                        : kv_scores_launch<ASVD_F16, Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                                         ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, (hipStream_t)stream);
     if (lrc != ASVD_OK) return lrc;
     if (scores_out) {
         hipLaunchKernelGGL(kv_scores_copy_kernel, dim3((unsigned)(B * H), (unsigned)ceil_div64(Tmax, 256)), dim3(256), 0, (hipStream_t)stream,
                            (const float*)((char*)work + p.off_s), (const int*)lens, (float*)scores_out, (int)H, (int)Tmax, (int)p.tld);
         ASVD_HIP_CHECK(hipGetLastError());
     }
+    return ASVD_OK;
+}
+
+// stages a - d of the whole op on checked arguments
+template <int ADT, bool Q8>
+int kv_decode_go(const KvPlan& p, const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
+                 const void* Av, const void* bv, const void* cos_tab, const void* sin_tab, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv,
+                 int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride,
+                 int64_t cv_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out,
+                 void* work, hipStream_t st) {
+    const int lrc = kv_scores_launch<ADT, Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                              ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, st);
+    if (lrc != ASVD_OK) return lrc;
+    const float* S = (const float*)((char*)work + p.off_s);
+    float* ml = (float*)((char*)work + p.off_ml);
+    float* Op = (float*)((char*)work + p.off_o);
+    hipLaunchKernelGGL((kv_pv_kernel<ADT, Q8>), dim3((unsigned)(B * (p.hpad / 32)), (unsigned)p.n_splits, (unsigned)ceil_div64(r_v, 128)), dim3(256), 0, st,
+                       S, cv, cv_row_stride, cv_batch_stride, (const float*)sv, sv_row_stride, sv_batch_stride, (const int*)lens, ml, Op, (int)H, (int)r_v,
+                       (int)Tmax, (int)p.hpad, (int)p.tld, (int)p.split_len, (int)p.n_splits);
+    hipLaunchKernelGGL((kv_combine_kernel<ADT>), dim3((unsigned)(B * H)), dim3(256), (size_t)r_v * sizeof(float), st, (const float*)ml, (const float*)Op,
+                       (const int*)lens, (const uint16_t*)Av, (const uint16_t*)bv, (uint16_t*)out, (int)H, (int)(H / H_kv), (int)D, (int)r_v,
+                       (int)Tmax, (int)p.hpad, (int)p.split_len, (int)p.n_splits);
+    ASVD_HIP_CHECK(hipGetLastError());
     return ASVD_OK;
 }
 
@@ -443,21 +500,13 @@ int kv_decode_entry(const void* q, const void* ck, const void* cv, const void* s
     if (rc != ASVD_OK) return rc;
     const KvPlan p = kv_plan(B, H, Tmax, r_k, r_v);
     if (work_bytes < p.total) return ASVD_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int lrc = kv_scores_launch<Q8>(p, q, ck, lens, Ak, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
-                                         ck_batch_stride, (const float*)sk, sk_row_stride, sk_batch_stride, work, st);
-    if (lrc != ASVD_OK) return lrc;
-    const float* S = (const float*)((char*)work + p.off_s);
-    float* ml = (float*)((char*)work + p.off_ml);
-    float* Op = (float*)((char*)work + p.off_o);
-    hipLaunchKernelGGL((kv_pv_kernel<Q8>), dim3((unsigned)(B * (p.hpad / 32)), (unsigned)p.n_splits, (unsigned)ceil_div64(r_v, 128)), dim3(256), 0, st, S,
-                       cv, cv_row_stride, cv_batch_stride, (const float*)sv, sv_row_stride, sv_batch_stride, (const int*)lens, ml, Op, (int)H, (int)r_v,
-                       (int)Tmax, (int)p.hpad, (int)p.tld, (int)p.split_len, (int)p.n_splits);
-    hipLaunchKernelGGL(kv_combine_kernel, dim3((unsigned)(B * H)), dim3(256), (size_t)r_v * sizeof(float), st, (const float*)ml, (const float*)Op,
-                       (const int*)lens, (const uint16_t*)Av, (const uint16_t*)bv, (uint16_t*)out, (int)H, (int)(H / H_kv), (int)D, (int)r_v,
-                       (int)Tmax, (int)p.hpad, (int)p.split_len, (int)p.n_splits);
-    ASVD_HIP_CHECK(hipGetLastError());
-    return ASVD_OK;
+    if (dtype == ASVD_BF16)
+        return kv_decode_go<ASVD_BF16, Q8>(p, q, ck, cv, sk, sv, lens, Ak, Av, bv, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
+                                           ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride, sv_row_stride,
+                                           sv_batch_stride, out, work, (hipStream_t)stream);
+    return kv_decode_go<ASVD_F16, Q8>(p, q, ck, cv, sk, sv, lens, Ak, Av, bv, cos_tab, sin_tab, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
+                                      ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride, sv_row_stride,
+                                      sv_batch_stride, out, work, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -479,28 +528,68 @@ int asvd_lowrank_kv_worksize(int64_t B, int64_t H, int64_t Tmax, int64_t r_k, in
     return ASVD_OK;
 }
 
+// K22: the _a16 entries take dtype ASVD_F16 or ASVD_BF16 (the type of q, A_k, A_v, the biases, the output and of an unquantised cache);
+// the entries without the suffix keep their fp16-only rule and forward
+int asvd_lowrank_kv_scores_a16(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                               const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k,
+                               int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, void* scores_out, void* work, size_t work_bytes,
+                               void* stream) {
+    return kv_scores_entry<false>(q, ck, nullptr, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                  ck_batch_stride, 0, 0, scores_out, work, work_bytes, stream);
+}
+
+int asvd_lowrank_kv_decode_a16(const void* q, const void* ck, const void* cv, const void* lens, const void* Ak, const void* Av, const void* bk,
+                               const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
+                               int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
+                               int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream) {
+    return kv_decode_entry<false>(q, ck, cv, nullptr, nullptr, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v,
+                                  Tmax, ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, 0, 0, 0, 0, out, work, work_bytes, stream);
+}
+
+// K21: the same stages on an int8 cache; ck / cv are codes (strides in bytes), sk / sv their fp32 group scales (strides in floats)
+int asvd_lowrank_kv_scores_q8_a16(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                                  const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D,
+                                  int64_t r_k, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride,
+                                  int64_t sk_batch_stride, void* scores_out, void* work, size_t work_bytes, void* stream) {
+    return kv_scores_entry<true>(q, ck, sk, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                 ck_batch_stride, sk_row_stride, sk_batch_stride, scores_out, work, work_bytes, stream);
+}
+
+int asvd_lowrank_kv_decode_q8_a16(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
+                                  const void* Av, const void* bk, const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode,
+                                  float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax,
+                                  int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride, int64_t cv_batch_stride,
+                                  int64_t sk_row_stride, int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work,
+                                  size_t work_bytes, void* stream) {
+    return kv_decode_entry<true>(q, ck, cv, sk, sv, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
+                                 ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride, sv_row_stride,
+                                 sv_batch_stride, out, work, work_bytes, stream);
+}
+
 int asvd_lowrank_kv_scores(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cos_tab, const void* sin_tab,
                            int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t Tmax,
                            int64_t ck_row_stride, int64_t ck_batch_stride, void* scores_out, void* work, size_t work_bytes, void* stream) {
-    return kv_scores_entry<false>(q, ck, nullptr, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
-                                  ck_batch_stride, 0, 0, scores_out, work, work_bytes, stream);
+    if (dtype != ASVD_F16) return ASVD_E_BADARG;
+    return asvd_lowrank_kv_scores_a16(q, ck, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                      ck_batch_stride, scores_out, work, work_bytes, stream);
 }
 
 int asvd_lowrank_kv_decode(const void* q, const void* ck, const void* cv, const void* lens, const void* Ak, const void* Av, const void* bk,
                            const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
                            int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
                            int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream) {
-    return kv_decode_entry<false>(q, ck, cv, nullptr, nullptr, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v,
-                                  Tmax, ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, 0, 0, 0, 0, out, work, work_bytes, stream);
+    if (dtype != ASVD_F16) return ASVD_E_BADARG;
+    return asvd_lowrank_kv_decode_a16(q, ck, cv, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
+                                      ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, out, work, work_bytes, stream);
 }
 
-// K21: the same stages on an int8 cache; ck / cv are codes (strides in bytes), sk / sv their fp32 group scales (strides in floats)
 int asvd_lowrank_kv_scores_q8(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
                               const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k,
                               int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride, int64_t sk_batch_stride,
                               void* scores_out, void* work, size_t work_bytes, void* stream) {
-    return kv_scores_entry<true>(q, ck, sk, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
-                                 ck_batch_stride, sk_row_stride, sk_batch_stride, scores_out, work, work_bytes, stream);
+    if (dtype != ASVD_F16) return ASVD_E_BADARG;
+    return asvd_lowrank_kv_scores_q8_a16(q, ck, sk, lens, Ak, bk, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, Tmax, ck_row_stride,
+                                         ck_batch_stride, sk_row_stride, sk_batch_stride, scores_out, work, work_bytes, stream);
 }
 
 int asvd_lowrank_kv_decode_q8(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
@@ -509,9 +598,10 @@ int asvd_lowrank_kv_decode_q8(const void* q, const void* ck, const void* cv, con
                               int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride, int64_t cv_batch_stride, int64_t sk_row_stride,
                               int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work, size_t work_bytes,
                               void* stream) {
-    return kv_decode_entry<true>(q, ck, cv, sk, sv, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v, Tmax,
-                                 ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride, sv_row_stride,
-                                 sv_batch_stride, out, work, work_bytes, stream);
+    if (dtype != ASVD_F16) return ASVD_E_BADARG;
+    return asvd_lowrank_kv_decode_q8_a16(q, ck, cv, sk, sv, lens, Ak, Av, bk, bv, cos_tab, sin_tab, dtype, rope_mode, scale, B, H, H_kv, D, r_k, r_v,
+                                         Tmax, ck_row_stride, ck_batch_stride, cv_row_stride, cv_batch_stride, sk_row_stride, sk_batch_stride,
+                                         sv_row_stride, sv_batch_stride, out, work, work_bytes, stream);
 }
 
 }  // extern "C"

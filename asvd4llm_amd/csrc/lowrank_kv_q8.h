@@ -5,6 +5,8 @@
 // Per group: amax = max |x|, s = amax / 127 (IEEE fp32 division), code = clamp(rintf(float(x) / s), -127, 127) as int8.  amax == 0 gives
 // s = 0 and codes 0; a NaN or Inf in the group gives s = NaN (0x7fc00000) and codes 0, so the whole group reads back as NaN.
 // Read back: d = fp16_rne(float(code) * s), one fp32 product and one rounding, defined for every int8 code.
+// The bf16 kernels (K22) use bf16_rne(d): the SAME format and the same d, rounded once more (a double rounding by design: it is the value
+// torch's dequantise-then-.bfloat16() gives, so kernel and torch path read one cache).
 #pragma once
 #include "common.h"
 
@@ -25,6 +27,19 @@ __device__ __forceinline__ f16x8 kv_q8_dequant8(uint2 c, float s) {
     for (int u = 0; u < 4; ++u) {
         d[u] = kv_q8_dequant((int)(int8_t)(c.x >> (8 * u)), s);
         d[4 + u] = kv_q8_dequant((int)(int8_t)(c.y >> (8 * u)), s);
+    }
+    return d;
+}
+
+// K22: the bits of bf16_rne(d)
+__device__ __forceinline__ uint16_t kv_q8_dequant_bf16(int code, float s) { return f32_to_bf16_bits((float)kv_q8_dequant(code, s)); }
+
+__device__ __forceinline__ f16x8 kv_q8_dequant8_bf16(uint2 c, float s) {   // f16x8 as the container of 8 bf16 values
+    f16x8 d;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        d[u] = __builtin_bit_cast(_Float16, kv_q8_dequant_bf16((int)(int8_t)(c.x >> (8 * u)), s));
+        d[4 + u] = __builtin_bit_cast(_Float16, kv_q8_dequant_bf16((int)(int8_t)(c.y >> (8 * u)), s));
     }
     return d;
 }

@@ -6,15 +6,25 @@ product (csrc/lowrank_kv.hip, K20; DESIGN.md 4 "K20").
 
   LowRankKVCache      preallocated C_k / C_v buffers per layer and the lengths, host and device side; quant="int8" keeps a layer as 8-bit
                       codes and one fp32 scale per token and 32 columns (K21, csrc/lowrank_kv_q8.hip; DESIGN.md 4 "K21")
-  LowRankKVAttention  prefill / decode of one attention layer on that cache; decode runs K20, or torch on the same cache on a refusal
+  LowRankKVAttention  prefill / decode of one attention layer on that cache; decode runs K20, or torch on the same cache on a refusal;
+                      a bf16 layer takes the kernel only when asked (kv_bf16 / ASVD_KV_BF16=1: K22, DESIGN.md 4 "K22")
   greedy_decode       a runner for Llama-family HF models that owns its loop (no transformers attention or cache class is patched)
 """
+
+import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+
+
+def kv_bf16_enabled():
+    """decode attention of a bf16 layer on the K20 kernels is opt-in (ASVD_KV_BF16=1, or kv_bf16=True on LowRankKVAttention / greedy_decode):
+    the bf16 form of csrc/lowrank_kv.hip (K22) rounds q~, p and the output to bf16 where torch's bf16 route rounds K, V and its own
+    intermediates, so the output bits of a bf16 model change with the switch.  Off, a bf16 layer answers "not fp16" and decodes in torch."""
+    return os.environ.get("ASVD_KV_BF16", "0") == "1"
 
 
 class FactorPair(nn.Module):
@@ -63,7 +73,9 @@ class _TokenCache:
 
     def _store(self, layer, seqs, t0, c, ck_rows, cv_rows):
         """rows [len(seqs), c, width] into positions t0 .. t0 + c of the sequences `seqs` (a slice).  An int8 layer quantises them: with the
-        kernel when they are fp16 on the device, with the same definition in torch otherwise (through .half())"""
+        kernel when they are fp16 or bf16 on the device (bf16 rows through .half(): the format is defined on fp16 values), with the same
+        definition in torch otherwise (through .half() as well).  Codes and scales are the same bits either way.  A bf16 latent beyond
+        65504 is an Inf in fp16 and turns its group into a NaN group, as it does in the torch definition."""
         if c == 0:
             return
         if not self.quant[layer]:
@@ -71,7 +83,9 @@ class _TokenCache:
             self.cv[layer][seqs, t0:t0 + c] = cv_rows
             return
         for codes, scales, rows in ((self.ck[layer], self.sk[layer], ck_rows), (self.cv[layer], self.sv[layer], cv_rows)):
-            if rows.is_cuda and rows.dtype == torch.float16:
+            if rows.is_cuda and rows.dtype in (torch.float16, torch.bfloat16):
+                if rows.dtype == torch.bfloat16:
+                    rows = rows.half()
                 if rows.stride(2) != 1 or rows.stride(1) % 8 or rows.stride(0) % 8 or rows.data_ptr() % 16:
                     rows = rows.contiguous()
                 ops.lowrank_kv_quant(rows, codes[seqs, t0:t0 + c], scales[seqs, t0:t0 + c])
@@ -155,9 +169,10 @@ def _plain_linear(m):
 class LowRankKVAttention(nn.Module):
     """One attention layer on a low-rank cache.  q_proj / o_proj: any module; k_proj / v_proj: modules with BLinear and ALinear
     (SVDLinear).  n_heads / n_kv_heads; scale (default D^-1/2); rope = None (no positional rotation: OPT) or (cos, sin) fp32 tables
-    [>= max_tokens, D/2] from ops.rope_table (Llama).  kernel=False keeps everything in torch (also on the CPU)."""
+    [>= max_tokens, D/2] from ops.rope_table (Llama).  kernel=False keeps everything in torch (also on the CPU).  kv_bf16: whether a bf16
+    layer (hidden, ALinear weights and biases all bf16) decodes on the kernel's bf16 form (K22); None reads ASVD_KV_BF16=1 (kv_bf16_enabled)."""
 
-    def __init__(self, q_proj, k_proj, v_proj, o_proj, n_heads, n_kv_heads=None, scale=None, rope=None, kernel=True):
+    def __init__(self, q_proj, k_proj, v_proj, o_proj, n_heads, n_kv_heads=None, scale=None, rope=None, kernel=True, kv_bf16=None):
         super().__init__()
         for name, m in (("k_proj", k_proj), ("v_proj", v_proj)):
             if not (hasattr(m, "BLinear") and hasattr(m, "ALinear")):
@@ -168,6 +183,7 @@ class LowRankKVAttention(nn.Module):
         self.scale = float(scale) if scale is not None else self.head_dim ** -0.5
         self.rope = rope
         self.kernel = bool(kernel)
+        self.kv_bf16 = kv_bf16_enabled() if kv_bf16 is None else bool(kv_bf16)
         self._work = {}
 
     @property
@@ -222,7 +238,10 @@ class LowRankKVAttention(nn.Module):
             return "hooks"
         if hidden.dim() != 3 or hidden.shape[1] != 1:
             return "token count"
-        if not (hidden.dtype == torch.float16 and kA.weight.dtype == torch.float16 and vA.weight.dtype == torch.float16):
+        if hidden.dtype == torch.bfloat16 and self.kv_bf16:   # K22: one dtype for the query, the factors and their biases
+            if any(t is not None and t.dtype != torch.bfloat16 for t in (kA.weight, vA.weight, kA.bias, vA.bias)):
+                return "mixed dtypes"
+        elif not (hidden.dtype == torch.float16 and kA.weight.dtype == torch.float16 and vA.weight.dtype == torch.float16):
             return "not fp16"
         if self.head_dim not in (64, 128) or self.n_heads % self.n_kv_heads:
             return "head size"
@@ -336,13 +355,32 @@ def kv_ranks(model):
     return out
 
 
+def decode_routes(model, kernel=True, kv_bf16=None):
+    """what greedy_decode(model, ..., cache="lowrank", kernel=kernel, kv_bf16=kv_bf16) does with a decode step, per layer: "kernel" (K20),
+    the refusal reason of LowRankKVAttention (torch on the low-rank cache), or "uncompressed" (the layer keeps its K and V).  Host only."""
+    cfg = model.config
+    H, H_kv = cfg.num_attention_heads, getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+    out = []
+    for l in model.model.layers:
+        a = l.self_attn
+        if not (_is_pair(a.k_proj) and _is_pair(a.v_proj)):
+            out.append("uncompressed")
+            continue
+        w = a.k_proj.ALinear.weight if hasattr(a.k_proj.ALinear, "weight") else None
+        probe = torch.empty(1, 1, 1, dtype=w.dtype if w is not None else torch.float16, device=w.device if w is not None else "cpu")
+        why = LowRankKVAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, 1.0, (None, None), kernel, kv_bf16).refusal(probe)   # rope: the runner always rotates
+        out.append("kernel" if why is None else why)
+    return out
+
+
 @torch.no_grad()
-def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=None, kv_quant=None):
+def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=None, kv_quant=None, kv_bf16=None):
     """Greedy decoding of a Llama-family HF model with this module's caches: prefill input_ids [B, n], then one token per step.
     cache="lowrank": where k_proj / v_proj are factor pairs the cache holds their BLinear outputs and decode steps run K20 (kernel=True) or
     torch on the same cache (kernel=False, also on the CPU); a layer the search left uncompressed keeps its K and V.  cache="dense": the ordinary K / V cache, any k_proj / v_proj.
     kv_quant="int8" (cache="lowrank" only): the layers whose k_proj and v_proj are both factor pairs keep their latents as int8 codes (K21) and
     decode on them; an uncompressed layer keeps its fp16 K and V.
+    kv_bf16: passed to LowRankKVAttention (a bf16 model's decode steps on the kernel, K22; None reads ASVD_KV_BF16=1).
     forced [B, n_new] (optional): the tokens fed back instead of the runner's own choices, to compare runs on one token stream.
     Returns (tokens [B, n_new], logits [n_new, B, vocab]): logits[s] chose tokens[:, s]."""
     if not is_llama_family(model):
@@ -368,7 +406,7 @@ def greedy_decode(model, input_ids, n_new, cache="lowrank", kernel=True, forced=
         pairs = [_is_pair(l.self_attn.k_proj) and _is_pair(l.self_attn.v_proj) for l in layers]
         # an uncompressed layer keeps K and V (never quantised) in its slot of the same cache
         kv = LowRankKVCache(len(layers), B, Tmax, kv_ranks(model), dev, dtype, quant=[kv_quant if p else None for p in pairs])
-        attn = [(LowRankKVAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, scale, rope, kernel) if _is_pair(a.k_proj) and _is_pair(a.v_proj)
+        attn = [(LowRankKVAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, scale, rope, kernel, kv_bf16) if _is_pair(a.k_proj) and _is_pair(a.v_proj)
                  else _DenseAttention(a.q_proj, a.k_proj, a.v_proj, a.o_proj, H, H_kv, scale, rope)) for a in (l.self_attn for l in layers)]
     else:
         kv = DenseKVCache(len(layers), B, Tmax, H_kv, D, dev, dtype)

@@ -837,9 +837,17 @@ def lowrank_kv_work(B, H, Tmax, r_k, r_v, device):
     return _work(nb.value, device)
 
 
-def _kv_cache_arg(name, c, B, dev):
-    if c.dim() != 3 or c.dtype != torch.float16 or c.shape[0] != B or c.stride(2) != 1 or c.device != dev:
-        raise ValueError(f"{name}: cache [B, Tmax, r] fp16 with unit rank stride on the device of q (got {tuple(c.shape)} {c.dtype})")
+KV_DTYPES = (torch.float16, torch.bfloat16)   # element types of K20 / K21: q, Ak, Av, the biases, out and an unquantised cache share ONE (bf16: K22)
+
+
+def _kv_name(dt):
+    return "bf16" if dt == torch.bfloat16 else "fp16"
+
+
+def _kv_cache_arg(name, c, B, dev, dt=torch.float16):
+    if c.dim() != 3 or c.dtype != dt or c.shape[0] != B or c.stride(2) != 1 or c.device != dev:
+        raise ValueError(f"{name}: cache [B, Tmax, r] {_kv_name(dt)} (the dtype of q) with unit rank stride on the device of q "
+                         f"(got {tuple(c.shape)} {c.dtype})")
     r = c.shape[2]
     if r < 16 or r % 16:
         raise ValueError(f"{name}: rank {r} is not a multiple of 16")
@@ -849,22 +857,24 @@ def _kv_cache_arg(name, c, B, dev):
 
 
 def _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv, r_k=None):
-    """r_k: given when the caller has checked the cache by rules of its own (an int8 cache, K21)"""
-    if q.dim() != 3 or q.dtype != torch.float16 or not q.is_contiguous():
-        raise ValueError(f"{name} needs q [B, H, D] fp16 contiguous (got {tuple(q.shape)} {q.dtype})")
+    """r_k: given when the caller has checked the cache by rules of its own (an int8 cache, K21).  q is fp16 or bf16 and every other
+    16-bit argument has q's dtype (the caller checks Av, bv and out against it)"""
+    if q.dim() != 3 or q.dtype not in KV_DTYPES or not q.is_contiguous():
+        raise ValueError(f"{name} needs q [B, H, D] fp16 or bf16 contiguous (got {tuple(q.shape)} {q.dtype})")
     B, H, D = q.shape
+    dt, dn = q.dtype, _kv_name(q.dtype)
     dev = q.device
     if D not in (64, 128) or H < 1 or H_kv < 1 or H % H_kv:
         raise ValueError(f"{name}: head size 64 or 128 and H_kv dividing H (got D {D}, H {H}, H_kv {H_kv})")
     if r_k is None:
-        r_k = _kv_cache_arg(name, ck, B, dev)
+        r_k = _kv_cache_arg(name, ck, B, dev, dt)
     Tmax = ck.shape[1]
     if lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous() or lens.device != dev:
         raise ValueError(f"{name} needs lens int32 [B] on the device of q")
-    if Ak.dtype != torch.float16 or tuple(Ak.shape) != (H_kv * D, r_k) or not Ak.is_contiguous() or Ak.device != dev or Ak.data_ptr() % 16:
-        raise ValueError(f"{name} needs Ak [H_kv * D, r_k] fp16 contiguous (got {tuple(Ak.shape)} {Ak.dtype})")
-    if bk is not None and (bk.dtype != torch.float16 or bk.numel() != H_kv * D or not bk.is_contiguous() or bk.device != dev):
-        raise ValueError(f"{name} needs bk [H_kv * D] fp16 contiguous or None")
+    if Ak.dtype != dt or tuple(Ak.shape) != (H_kv * D, r_k) or not Ak.is_contiguous() or Ak.device != dev or Ak.data_ptr() % 16:
+        raise ValueError(f"{name} needs Ak [H_kv * D, r_k] {dn} (the dtype of q) contiguous (got {tuple(Ak.shape)} {Ak.dtype})")
+    if bk is not None and (bk.dtype != dt or bk.numel() != H_kv * D or not bk.is_contiguous() or bk.device != dev):
+        raise ValueError(f"{name} needs bk [H_kv * D] {dn} (the dtype of q) contiguous or None")
     mode, cos, sin = "none", None, None
     if rope is not None:
         mode, (cos, sin) = "half", rope
@@ -876,10 +886,31 @@ def _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv, r_k=None):
     return B, H, D, r_k, Tmax, mode, cos, sin
 
 
+def _kv_value_args(name, q, Av, bv, out, H_kv, r_v):
+    """Av, bv and a given out against q: one dtype"""
+    B, H, D = q.shape
+    dt, dn, dev = q.dtype, _kv_name(q.dtype), q.device
+    if Av.dtype != dt or tuple(Av.shape) != (H_kv * D, r_v) or not Av.is_contiguous() or Av.device != dev or Av.data_ptr() % 16:
+        raise ValueError(f"{name} needs Av [H_kv * D, r_v] {dn} (the dtype of q) contiguous (got {tuple(Av.shape)} {Av.dtype})")
+    if bv is not None and (bv.dtype != dt or bv.numel() != H_kv * D or not bv.is_contiguous() or bv.device != dev):
+        raise ValueError(f"{name} needs bv [H_kv * D] {dn} (the dtype of q) contiguous or None")
+    if out is not None and (out.dtype != dt or tuple(out.shape) != (B, H, D) or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"{name}: out must be [B, H, D] {dn} (the dtype of q) contiguous on the device of q")
+
+
+def _kv_entry(lib, name, q):
+    """(the C entry, its dtype code): fp16 calls keep the K20 / K21 entries, bf16 goes to their _a16 forms (K22)"""
+    if q.dtype == torch.bfloat16:
+        return getattr(lib, name + "_a16"), L.BF16, name + "_a16"
+    return getattr(lib, name), L.F16, name
+
+
 def lowrank_kv_scores(q, ck, lens, Ak, H_kv, scale, bk=None, rope=None, work=None):
     """S [B, H, Tmax] fp32 = scale * q_h . K_h[t] with K_h = C_k A_k[kv(h)]^T (rotated by rope = (cos, sin) tables when given), zeros at
     t >= lens[b] (K20 stages a and b, asvd_lowrank_kv_scores).  q [B, H, D] fp16 (already rotated), ck [B, Tmax, r_k] fp16 (strided views with
-    16-byte aligned rows are fine), lens int32 [B], Ak [H_kv * D, r_k] fp16.  Every argument check comes before the device is asked for."""
+    16-byte aligned rows are fine), lens int32 [B], Ak [H_kv * D, r_k] fp16.  Every argument check comes before the device is asked for.
+    All of q, ck, Ak, bk may be bf16 instead (K22, asvd_lowrank_kv_scores_a16: q~ is rounded to bf16, the product runs on the bf16 MFMA); mixed
+    dtypes and fp32 are a ValueError."""
     B, H, D, r_k, Tmax, mode, cos, sin = _kv_args("lowrank_kv_scores", q, ck, lens, Ak, bk, rope, H_kv)
     _dev(q, "q")
     lib = L.load(True)
@@ -888,38 +919,35 @@ def lowrank_kv_scores(q, ck, lens, Ak, H_kv, scale, bk=None, rope=None, work=Non
         work = lowrank_kv_work(B, H, Tmax, r_k, 16, dev)
     out = torch.empty((B, H, Tmax), dtype=torch.float32, device=dev)
     with _on(dev):
-        L.check(lib.asvd_lowrank_kv_scores(q.data_ptr(), ck.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin), L.F16,
-                                           KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), out.data_ptr(),
-                                           work.data_ptr(), work.numel(), _stream(q)), "asvd_lowrank_kv_scores")
+        fn, dtc, fname = _kv_entry(lib, "asvd_lowrank_kv_scores", q)
+        L.check(fn(q.data_ptr(), ck.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin), dtc, KV_ROPE[mode], float(scale), B, H,
+                   H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)), fname)
     return out
 
 
 def lowrank_kv_decode(q, ck, cv, lens, Ak, Av, H_kv, scale, bk=None, bv=None, rope=None, work=None, out=None):
     """out [B, H, D] fp16 = softmax over t < lens[b] of the scores above, times V_h = C_v A_v[kv(h)]^T + b_v, for ONE new query token per
     sequence (K20, asvd_lowrank_kv_decode).  cv [B, Tmax, r_v] fp16 like ck, Av [H_kv * D, r_v] fp16.  A sequence with lens[b] == 0 gets
-    zeros.  Asynchronous on the current stream, no host sync, graph-capturable when `work` and `out` are given."""
+    zeros.  Asynchronous on the current stream, no host sync, graph-capturable when `work` and `out` are given.
+    All of q, ck, cv, Ak, Av, bk, bv and out may be bf16 instead (K22, asvd_lowrank_kv_decode_a16): q~, p and out are rounded to bf16 (RNE) where
+    the fp16 form rounds to fp16, on the bf16 MFMA, with the same sums in the same order.  Mixed dtypes and fp32 are a ValueError."""
     B, H, D, r_k, Tmax, mode, cos, sin = _kv_args("lowrank_kv_decode", q, ck, lens, Ak, bk, rope, H_kv)
     dev = q.device
-    r_v = _kv_cache_arg("lowrank_kv_decode", cv, B, dev)
+    r_v = _kv_cache_arg("lowrank_kv_decode", cv, B, dev, q.dtype)
     if cv.shape[1] != Tmax:
         raise ValueError("lowrank_kv_decode: ck and cv hold different token counts")
-    if Av.dtype != torch.float16 or tuple(Av.shape) != (H_kv * D, r_v) or not Av.is_contiguous() or Av.device != dev or Av.data_ptr() % 16:
-        raise ValueError(f"lowrank_kv_decode needs Av [H_kv * D, r_v] fp16 contiguous (got {tuple(Av.shape)} {Av.dtype})")
-    if bv is not None and (bv.dtype != torch.float16 or bv.numel() != H_kv * D or not bv.is_contiguous() or bv.device != dev):
-        raise ValueError("lowrank_kv_decode needs bv [H_kv * D] fp16 contiguous or None")
+    _kv_value_args("lowrank_kv_decode", q, Av, bv, out, H_kv, r_v)
     _dev(q, "q")
     lib = L.load(True)
     if work is None:
         work = lowrank_kv_work(B, H, Tmax, r_k, r_v, dev)
     if out is None:
-        out = torch.empty((B, H, D), dtype=torch.float16, device=dev)
-    elif out.dtype != torch.float16 or tuple(out.shape) != (B, H, D) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("lowrank_kv_decode: out must be [B, H, D] fp16 contiguous on the device of q")
+        out = torch.empty((B, H, D), dtype=q.dtype, device=dev)
     with _on(dev):
-        L.check(lib.asvd_lowrank_kv_decode(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), lens.data_ptr(), Ak.data_ptr(), Av.data_ptr(), _ptr(bk),
-                                           _ptr(bv), _ptr(cos), _ptr(sin), L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, r_v, Tmax,
-                                           ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(),
-                                           _stream(q)), "asvd_lowrank_kv_decode")
+        fn, dtc, fname = _kv_entry(lib, "asvd_lowrank_kv_decode", q)
+        L.check(fn(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), lens.data_ptr(), Ak.data_ptr(), Av.data_ptr(), _ptr(bk), _ptr(bv), _ptr(cos), _ptr(sin),
+                   dtc, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, r_v, Tmax, ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0),
+                   out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)), fname)
     return out
 
 
@@ -1009,13 +1037,14 @@ def lowrank_kv_quant(x, codes_out, scales_out):
 def _kv_args_q8(name, q, ck, sk, lens, Ak, bk, rope, H_kv):
     """_kv_args for an int8 key cache: the same rules, with _kv_q8_arg's in place of the fp16 cache's"""
     if q.dim() != 3:
-        raise ValueError(f"{name} needs q [B, H, D] fp16 contiguous (got {tuple(q.shape)} {q.dtype})")
+        raise ValueError(f"{name} needs q [B, H, D] fp16 or bf16 contiguous (got {tuple(q.shape)} {q.dtype})")
     return _kv_args(name, q, ck, lens, Ak, bk, rope, H_kv, r_k=_kv_q8_arg(name, ck, sk, q.shape[0], q.device))
 
 
 def lowrank_kv_scores_q8(q, ck, sk, lens, Ak, H_kv, scale, bk=None, rope=None, work=None):
     """lowrank_kv_scores on an int8 cache: ck int8 codes [B, Tmax, r_k] and sk fp32 scales [B, Tmax, >= ceil(r_k / 32)] (K21,
-    asvd_lowrank_kv_scores_q8).  The bits of lowrank_kv_scores(q, lowrank_kv_dequant(ck, sk), ...)."""
+    asvd_lowrank_kv_scores_q8).  The bits of lowrank_kv_scores(q, lowrank_kv_dequant(ck, sk), ...).  With bf16 q, Ak, bk (K22,
+    asvd_lowrank_kv_scores_q8_a16): the bits of the bf16 call on lowrank_kv_dequant(ck, sk).bfloat16(), the same codes rounded twice."""
     B, H, D, r_k, Tmax, mode, cos, sin = _kv_args_q8("lowrank_kv_scores_q8", q, ck, sk, lens, Ak, bk, rope, H_kv)
     _dev(q, "q")
     lib = L.load(True)
@@ -1024,39 +1053,37 @@ def lowrank_kv_scores_q8(q, ck, sk, lens, Ak, H_kv, scale, bk=None, rope=None, w
         work = lowrank_kv_work(B, H, Tmax, r_k, 16, dev)
     out = torch.empty((B, H, Tmax), dtype=torch.float32, device=dev)
     with _on(dev):
-        L.check(lib.asvd_lowrank_kv_scores_q8(q.data_ptr(), ck.data_ptr(), sk.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin),
-                                              L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), sk.stride(1),
-                                              sk.stride(0), out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)), "asvd_lowrank_kv_scores_q8")
+        fn, dtc, fname = _kv_entry(lib, "asvd_lowrank_kv_scores_q8", q)
+        L.check(fn(q.data_ptr(), ck.data_ptr(), sk.data_ptr(), lens.data_ptr(), Ak.data_ptr(), _ptr(bk), _ptr(cos), _ptr(sin), dtc, KV_ROPE[mode],
+                   float(scale), B, H, H_kv, D, r_k, Tmax, ck.stride(1), ck.stride(0), sk.stride(1), sk.stride(0), out.data_ptr(), work.data_ptr(),
+                   work.numel(), _stream(q)), fname)
     return out
 
 
 def lowrank_kv_decode_q8(q, ck, cv, sk, sv, lens, Ak, Av, H_kv, scale, bk=None, bv=None, rope=None, work=None, out=None):
     """lowrank_kv_decode on an int8 cache: ck / cv int8 codes, sk / sv their fp32 group scales (K21, asvd_lowrank_kv_decode_q8).  The bits of
-    lowrank_kv_decode on the dequantised cache; same workspace (lowrank_kv_work), asynchronous, graph-capturable when `work` and `out` are given."""
+    lowrank_kv_decode on the dequantised cache; same workspace (lowrank_kv_work), asynchronous, graph-capturable when `work` and `out` are given.
+    With bf16 q, Ak, Av, bk, bv, out (K22, asvd_lowrank_kv_decode_q8_a16): the bits of the bf16 lowrank_kv_decode on
+    lowrank_kv_dequant(codes, scales).bfloat16(); the cache format does not change."""
     name = "lowrank_kv_decode_q8"
     B, H, D, r_k, Tmax, mode, cos, sin = _kv_args_q8(name, q, ck, sk, lens, Ak, bk, rope, H_kv)
     dev = q.device
     r_v = _kv_q8_arg(name, cv, sv, B, dev)
     if cv.shape[1] != Tmax:
         raise ValueError(f"{name}: ck and cv hold different token counts")
-    if Av.dtype != torch.float16 or tuple(Av.shape) != (H_kv * D, r_v) or not Av.is_contiguous() or Av.device != dev or Av.data_ptr() % 16:
-        raise ValueError(f"{name} needs Av [H_kv * D, r_v] fp16 contiguous (got {tuple(Av.shape)} {Av.dtype})")
-    if bv is not None and (bv.dtype != torch.float16 or bv.numel() != H_kv * D or not bv.is_contiguous() or bv.device != dev):
-        raise ValueError(f"{name} needs bv [H_kv * D] fp16 contiguous or None")
-    if out is not None and (out.dtype != torch.float16 or tuple(out.shape) != (B, H, D) or not out.is_contiguous() or out.device != dev):
-        raise ValueError(f"{name}: out must be [B, H, D] fp16 contiguous on the device of q")
+    _kv_value_args(name, q, Av, bv, out, H_kv, r_v)
     _dev(q, "q")
     lib = L.load(True)
     if work is None:
         work = lowrank_kv_work(B, H, Tmax, r_k, r_v, dev)
     if out is None:
-        out = torch.empty((B, H, D), dtype=torch.float16, device=dev)
+        out = torch.empty((B, H, D), dtype=q.dtype, device=dev)
     with _on(dev):
-        L.check(lib.asvd_lowrank_kv_decode_q8(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), sk.data_ptr(), sv.data_ptr(), lens.data_ptr(), Ak.data_ptr(),
-                                              Av.data_ptr(), _ptr(bk), _ptr(bv), _ptr(cos), _ptr(sin), L.F16, KV_ROPE[mode], float(scale), B, H, H_kv, D,
-                                              r_k, r_v, Tmax, ck.stride(1), ck.stride(0), cv.stride(1), cv.stride(0), sk.stride(1), sk.stride(0),
-                                              sv.stride(1), sv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(), _stream(q)),
-                "asvd_lowrank_kv_decode_q8")
+        fn, dtc, fname = _kv_entry(lib, "asvd_lowrank_kv_decode_q8", q)
+        L.check(fn(q.data_ptr(), ck.data_ptr(), cv.data_ptr(), sk.data_ptr(), sv.data_ptr(), lens.data_ptr(), Ak.data_ptr(), Av.data_ptr(), _ptr(bk),
+                   _ptr(bv), _ptr(cos), _ptr(sin), dtc, KV_ROPE[mode], float(scale), B, H, H_kv, D, r_k, r_v, Tmax, ck.stride(1), ck.stride(0),
+                   cv.stride(1), cv.stride(0), sk.stride(1), sk.stride(0), sv.stride(1), sv.stride(0), out.data_ptr(), work.data_ptr(), work.numel(),
+                   _stream(q)), fname)
     return out
 
 

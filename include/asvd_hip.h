@@ -630,6 +630,34 @@ int asvd_lowrank_kv_decode_q8(const void* q, const void* ck, const void* cv, con
                               int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work, size_t work_bytes,
                               void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K22: the four entries above for a bf16 model (csrc/lowrank_kv.hip, DESIGN.md 4 "K22").  Same argument lists, same rules, same workspace, same
+ * error codes, every check before any device call; dtype is ASVD_F16 or ASVD_BF16 and names the type of q, Ak, Av, bk, bv, out and, for the
+ * unquantised cache, of ck / cv.  With ASVD_F16 they ARE the entries above (which keep refusing every other dtype and forward here).  With ASVD_BF16:
+ *   q~ = bf16(A_k^T q), p = bf16(exp(S - max)) (the sum l runs over the rounded p), out = bf16(acc / l + b_v): one round-to-nearest-even where
+ *   the fp16 form rounds to fp16; every product is v_mfma_f32_32x32x16_bf16 with fp32 accumulation in the fp16 form's order; the rotation of mode
+ *   HALF and the scores stay fp32; plan, workspace layout (q~ is two bytes either way), launch geometry and masking are unchanged.
+ *   On an int8 cache the format does not change; a code's value is bf16_rne(fp16_rne(float(code) * s)), K21's value rounded once more
+ *   (a double rounding by design: it is what dequantising to fp16 and converting to bf16 gives). */
+int asvd_lowrank_kv_scores_a16(const void* q, const void* ck, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                               const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k,
+                               int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, void* scores_out, void* work, size_t work_bytes,
+                               void* stream);
+int asvd_lowrank_kv_decode_a16(const void* q, const void* ck, const void* cv, const void* lens, const void* Ak, const void* Av, const void* bk,
+                               const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H,
+                               int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride,
+                               int64_t cv_row_stride, int64_t cv_batch_stride, void* out, void* work, size_t work_bytes, void* stream);
+int asvd_lowrank_kv_scores_q8_a16(const void* q, const void* ck, const void* sk, const void* lens, const void* Ak, const void* bk, const void* cos_tab,
+                                  const void* sin_tab, int dtype, int rope_mode, float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D,
+                                  int64_t r_k, int64_t Tmax, int64_t ck_row_stride, int64_t ck_batch_stride, int64_t sk_row_stride,
+                                  int64_t sk_batch_stride, void* scores_out, void* work, size_t work_bytes, void* stream);
+int asvd_lowrank_kv_decode_q8_a16(const void* q, const void* ck, const void* cv, const void* sk, const void* sv, const void* lens, const void* Ak,
+                                  const void* Av, const void* bk, const void* bv, const void* cos_tab, const void* sin_tab, int dtype, int rope_mode,
+                                  float scale, int64_t B, int64_t H, int64_t H_kv, int64_t D, int64_t r_k, int64_t r_v, int64_t Tmax,
+                                  int64_t ck_row_stride, int64_t ck_batch_stride, int64_t cv_row_stride, int64_t cv_batch_stride,
+                                  int64_t sk_row_stride, int64_t sk_batch_stride, int64_t sv_row_stride, int64_t sv_batch_stride, void* out, void* work,
+                                  size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

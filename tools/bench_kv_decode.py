@@ -15,7 +15,12 @@ output (both are fp16 routes to the same value).
 --quant int8 adds a third pass per shape: the same latents as int8 codes and one fp32 scale per token and 32 columns (K21: quantised by
 asvd_lowrank_kv_quant, decoded by asvd_lowrank_kv_decode_q8), alternating with the other two, eager and graph-replayed; its cache bytes per token,
 its time over the fp16 low-rank route's of the same run, and the largest difference of its output from the fp16 low-rank route's.  The run that
-profiles/lowrank_kv_q8.json holds: python tools/bench_kv_decode.py --quant int8 > profiles/lowrank_kv_q8.json"""
+profiles/lowrank_kv_q8.json holds: python tools/bench_kv_decode.py --quant int8 > profiles/lowrank_kv_q8.json
+
+--dtype bf16 runs every pass in bf16 (K22): a bf16 dense baseline (bf16 K / V through torch SDPA), the bf16 low-rank route
+(asvd_lowrank_kv_decode_a16) and, with --quant int8, the bf16 route on the same int8 format (the latents are quantised from their fp16
+conversion, as the cache class does).  A run of one dtype holds no time of the other: for bf16 against fp16 run the tool once per dtype back to
+back.  profiles/lowrank_kv_bf16.json holds {"bf16": <the --dtype bf16 --quant int8 line>, "fp16": <the --quant int8 line of the same session>}."""
 import argparse
 import json
 import os
@@ -71,8 +76,9 @@ def one_shape(dev, H, D, r, T, B, mode, args):
     layers = max(1, min(args.max_layers, -(-(512 << 20) // min(low_layer, dense_layer))))
     rope = ops.rope_table(T, D, 10000.0, dev) if mode == "half" else None
     g = torch.Generator(device=dev).manual_seed(1)
-    rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float16)
-    Ak, Av = (rnd(H * D, r).float() / r ** 0.5).half(), (rnd(H * D, r).float() / r ** 0.5).half()
+    dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    rnd = lambda *s: torch.randn(*s, generator=g, device=dev, dtype=torch.float16).to(dt)   # one stream of draws for both dtypes
+    Ak, Av = (rnd(H * D, r).float() / r ** 0.5).to(dt), (rnd(H * D, r).float() / r ** 0.5).to(dt)
     lens = torch.full((B,), T, dtype=torch.int32, device=dev)
     q = rnd(B, H, D)
     ck, cv, Ks, Vs = [], [], [], []
@@ -81,7 +87,7 @@ def one_shape(dev, H, D, r, T, B, mode, args):
         cv.append(rnd(B, T, r))
         K = F.linear(ck[-1], Ak).view(B, T, H, D)
         if rope is not None:
-            K = rotate_half(K.float(), rope[0][None, :, None, :], rope[1][None, :, None, :]).half()
+            K = rotate_half(K.float(), rope[0][None, :, None, :], rope[1][None, :, None, :]).to(dt)
         Ks.append(K.transpose(1, 2).contiguous())
         Vs.append(F.linear(cv[-1], Av).view(B, T, H, D).transpose(1, 2).contiguous())
     q8 = []
@@ -90,11 +96,11 @@ def one_shape(dev, H, D, r, T, B, mode, args):
             t = [torch.empty(B, T, r, dtype=torch.int8, device=dev), torch.empty(B, T, r, dtype=torch.int8, device=dev),
                  torch.empty(B, T, ops.lowrank_kv_groups(r), dtype=torch.float32, device=dev),
                  torch.empty(B, T, ops.lowrank_kv_groups(r), dtype=torch.float32, device=dev)]
-            ops.lowrank_kv_quant(ck[i], t[0], t[2])
-            ops.lowrank_kv_quant(cv[i], t[1], t[3])
+            ops.lowrank_kv_quant(ck[i].half(), t[0], t[2])   # the format is defined on fp16 values
+            ops.lowrank_kv_quant(cv[i].half(), t[1], t[3])
             q8.append(t)
     work = ops.lowrank_kv_work(B, H, T, r, r, dev)
-    out = torch.empty(B, H, D, dtype=torch.float16, device=dev)
+    out = torch.empty(B, H, D, dtype=dt, device=dev)
     q4 = q[:, :, None, :]
 
     def k20():
@@ -111,7 +117,7 @@ def one_shape(dev, H, D, r, T, B, mode, args):
 
     ref = F.scaled_dot_product_attention(q4, Ks[0], Vs[0], scale=scale)[:, :, 0].float()
     got = ops.lowrank_kv_decode(q, ck[0], cv[0], lens, Ak, Av, H, scale, rope=rope).float()
-    rec = {"H": H, "D": D, "r_k": r, "r_v": r, "T": T, "B": B, "rope": mode, "layers": layers,
+    rec = {"dtype": args.dtype, "H": H, "D": D, "r_k": r, "r_v": r, "T": T, "B": B, "rope": mode, "layers": layers,
            "cache_bytes_per_token_layer": {"lowrank": 2 * r * 2, "dense": 2 * H * D * 2},
            "max_diff_over_max_out": float((got - ref).abs().max() / ref.abs().max())}
     # what one K20 step must move and compute, per layer: both caches once, both ALinear weights once per sequence at most (once if they
@@ -156,6 +162,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--max_layers", type=int, default=16)
+    ap.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16", help="bf16: every pass in bf16 (K22: the asvd_lowrank_kv_*_a16 entries)")
     ap.add_argument("--quant", choices=["none", "int8"], default="none", help="int8: a third pass on the int8 form of the low-rank cache (K21)")
     args = ap.parse_args()
     L.load(require_device=True)
@@ -169,7 +176,7 @@ def main():
                         recs.append(one_shape(dev, H, args.head_dim, r, T, B, mode, args))
                         print(f"[bench_kv_decode] {json.dumps(recs[-1])}", file=sys.stderr, flush=True)
                         torch.cuda.empty_cache()
-    print(json.dumps({"bench": "kv_decode", "device": torch.cuda.get_device_name(0), "runs": 1, "iters_per_run": args.iters, "warmup": args.warmup, "quant": args.quant,
+    print(json.dumps({"bench": "kv_decode", "device": torch.cuda.get_device_name(0), "runs": 1, "iters_per_run": args.iters, "warmup": args.warmup, "quant": args.quant, "dtype": args.dtype,
                       "timing": "device events around one pass over `layers` layers, the routes alternating; per-layer microseconds",
                       "results": recs}))
 
